@@ -14,7 +14,14 @@ into every rank's IPC-mapped device buffer over xGMI, where a totaler wave per r
 fixed-order total (--transport xgmi, default, r05), or through a node-wide shared-memory segment
 that every host totals (--transport shm), or one RCCL all-gather per pass (--transport rccl).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--n-source S] [--n-target T]
+A plain run sets up, warms up, times the K steps and prints the result line (the headline roofline row
+comes from the timed steps' own server events).  --full adds every other leg after the timed steps: the
+kernel-time and pass-bench rooflines, Gauss-Newton mode, the new-clouds / cold-pair / GICPState cycles,
+the C5 pass, the FOD rows, the CPU baselines and the parity against the oracle.  --dump-outputs DIR
+writes what the last timed align returned as DIR/<name>.npy.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--n-source S] [--n-target T] [--full]
+                       [--dump-outputs DIR]
        (N > 1: this script starts its own N ranks, or runs under torch.distributed.run)
 """
 from __future__ import annotations
@@ -105,7 +112,24 @@ def parse():
     ap.add_argument("--no-rccl", action="store_true",
                     help="N > 1: skip RCCL (the path a failed ncclCommInitRank falls back to: RCCL-free shards, "
                          "target covariances on every rank, rows through the segment / xGMI)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg: kernel-time (HIP event) and pass-bench "
+                         "rooflines, Gauss-Newton mode, new-clouds / cold-pair / GICPState cycles, the C5 pass, the "
+                         "FOD rows, the CPU baselines and the oracle parity (--cpu-sample, --oracle-full, "
+                         "--gn-steps, --fod-cpu-sample, --no-events, --pass-bench, --prof-steps, --cold-pairs and "
+                         "--c5-leg shape those legs and mean nothing without --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed align returned as DIR/<name>.npy (rank 0): "
+                         "final_transformation (4x4 f32), iteration_transformations (iterations x 4x4 f32), "
+                         "align_result (f64: converged, iterations, accepted correspondences)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        # a plain run does only what `value` needs: set up, warm up, the timed steps, the result line
+        args.cpu_sample = args.fod_cpu_sample = args.oracle_full = args.gn_steps = 0
+        args.pass_bench = args.cold_pairs = args.c5_leg = 0
+        args.no_events = True
     cfg = CONFIGS[args.config]
     args.n_source = args.n_source or cfg["n_source"]
     args.n_target = args.n_target or cfg["n_target"]
@@ -309,6 +333,19 @@ def fod_rows(eng, scan, cad, T_final, n_cpu):
     return rows
 
 
+def dump_outputs(out_dir, eng, T, max_iter):
+    """--dump-outputs: what the last timed align handed its caller, as .npy files (a few hundred
+    bytes; the clouds are seeded, so two builds run with the same arguments compare file for file)."""
+    r = eng.last_result
+    trace = eng.debug_trace(max_iter + 1)  # the transform after every outer iteration of that align
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "final_transformation.npy"), np.asarray(T, np.float32))
+    np.save(os.path.join(out_dir, "iteration_transformations.npy"),
+            np.asarray(trace, np.float32).reshape(-1, 4, 4))
+    np.save(os.path.join(out_dir, "align_result.npy"),
+            np.array([r["converged"], r["iterations"], r["n_corr"]], np.float64))
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -390,12 +427,14 @@ def main():
     total_iters = 0
     n_evals = 0
     for _ in range(args.steps):
-        eng.align()
+        T_timed = eng.align()
         total_iters += eng.last_result["iterations"]
         n_evals += eng.last_result["n_evals"]
     pg.barrier()
     dt = time.perf_counter() - t0
     dt = pg.allreduce_max(dt)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, T_timed, args.max_iter)
     # which pass path the timed aligns ran: every pass on the resident server,
     # none taken over by a launched pass; and the server's own in-align time per pass (two HIP events
     # per server launch on the engine stream -- launch to exit, host round trips between passes
@@ -480,7 +519,7 @@ def main():
     # with covariance-kernel events on (the timed region above runs with cached covariances)
     eng2 = None
     new_clouds = None
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         # wall time as a caller sees it (no instrumentation: the profiling mode turns the resident
         # pass server off), then the covariance kernels' times from a profiled repeat
         eng2 = GICPEngine(device=local, max_iter=args.max_iter, fixed_iterations=int(args.fixed),
@@ -748,6 +787,10 @@ def main():
         "fdf": kt["fdf"],
         "reduce_finish": kt["reduce_finish"],
     }
+    if not args.full:
+        # no kernel-time or pass-bench leg ran: only the rows taken from the timed steps themselves hold figures
+        rooflines = {k: rooflines[k] for k in ("fdf_52B", "fdf_72B_read_rate")}
+        kernels = None
 
     fod = fod_rows(eng, scan, cad, T_final, args.fod_cpu_sample) if args.fod_cpu_sample > 0 and world == 1 else None
     cpu = None
@@ -836,6 +879,7 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": bool(args.full),
         "ms_per_step": round(1e3 * dt / args.steps, 3),
         "higher_is_better": True,
         "scaling": "strong",

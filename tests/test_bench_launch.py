@@ -25,6 +25,62 @@ def test_bench_spawns_its_own_ranks(n):
     assert rec["local_rank"] == 0 and rec["shm_name"].startswith("/mgicp_")
 
 
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) at a small size: --steps sets the timed steps, the line holds the headline
+    fields and none of the --full legs, and --dump-outputs writes the last timed align's arrays."""
+    import numpy as np
+
+    out_dir = tmp_path / "out"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+           "--n-source", "20000", "--n-target", "20000", "--dump-outputs", str(out_dir)]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=120, env=env, cwd=ROOT)
+    assert out.returncode == 0, out.stderr
+    lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1
+    rec = json.loads(lines[0])
+    assert rec["steps"] == 2 and rec["warmup"] == 1 and rec["full"] is False
+    assert rec["unit"] == "iterations/s" and rec["higher_is_better"] is True and rec["value"] > 0
+    assert rec["dtype"] == "f32 transform / f64 accumulate"
+    assert rec["ms_per_step"] > 0
+    # value = iterations of the timed steps / their seconds, ms_per_step = those seconds / steps (both
+    # rounded to 3 decimals in the line)
+    assert rec["value"] == pytest.approx(rec["iterations_per_align"] / (rec["ms_per_step"] * 1e-3), rel=5e-3)
+    for leg in ("cpu_baseline", "gn_mode", "fod_rows", "cold_pair", "gicpstate_cycles", "parity_full_size",
+                "ms_to_converge_new_clouds_warm_process", "kernels", "frob_vs_oracle", "frob_vs_oracle_sample"):
+        assert rec[leg] is None, leg
+    assert sorted(p.name for p in out_dir.iterdir()) == ["align_result.npy", "final_transformation.npy",
+                                                         "iteration_transformations.npy"]
+    T = np.load(out_dir / "final_transformation.npy")
+    tr = np.load(out_dir / "iteration_transformations.npy")
+    res = np.load(out_dir / "align_result.npy")
+    assert T.dtype == np.float32 and T.shape == (4, 4) and np.isfinite(T).all()
+    assert tuple(T[3]) == (0.0, 0.0, 0.0, 1.0)
+    assert tr.dtype == np.float32 and tr.shape[1:] == (4, 4) and np.isfinite(tr).all()
+    assert res.dtype == np.float64 and res.shape == (3,)
+    assert res[1] == rec["iterations_per_align"] and res[2] == rec["n_corr"]
+    assert len(tr) == rec["iterations_per_align"]
+    np.testing.assert_array_equal(tr[-1], T)
+
+
+def test_bench_legs_beyond_the_timed_steps_wait_for_full():
+    """parse(): without --full every leg option is off whatever its own default; with --full they hold."""
+    code = ("import sys, json, bench\n"
+            "a = bench.parse()\n"
+            "print(json.dumps([a.full, a.cpu_sample, a.fod_cpu_sample, a.oracle_full, a.gn_steps, a.pass_bench, "
+            "a.cold_pairs, a.c5_leg, a.no_events, a.dump_outputs]))\n")
+    got = {}
+    for extra in ([], ["--full"], ["--full", "--gn-steps", "0", "--dump-outputs", "d"]):
+        out = subprocess.run([sys.executable, "-c", code, "--gpus", "1", "--steps", "3", "--warmup", "1"] + extra,
+                             capture_output=True, text=True, timeout=60, cwd=ROOT)
+        assert out.returncode == 0, out.stderr
+        got[len(extra)] = json.loads(out.stdout)
+    assert got[0] == [False, 0, 0, 0, 0, 0, 0, 0, True, None]
+    assert got[1] == [True, 500_000, 500_000, 1, 5, 5, 3, 1, False, None]
+    assert got[5] == [True, 500_000, 500_000, 1, 0, 5, 3, 1, False, "d"]
+
+
 def test_bench_launch_never_loads_the_engine_in_the_parent():
     """The parent of the spawned ranks must not load libmgicp.so (HIP) -- it only spawns and waits."""
     import ast
