@@ -284,8 +284,7 @@ int mgicp_set_profiling(mgicp_ctx* ctx, int on);
  * environment): "resident", "host_rows", "srv_cus", "fused_finish", "gated", "bar_cmd" (the
  * objective-pass path), "async_cov", "lazy_src_cov", "knn_logged", "knn_wave" (covariances), "vlist",
  * "vlist_cold", "vlist_eager", "vlist_stats", "fuse_compact" (1-NN cell lists),
- * "target_cache", "grid_occ" (grid
- * sizing of the next set_*).  Every form gives the default path's results bit for bit (the GPU tests
+ * "target_cache".  Every form gives the default path's results bit for bit (the GPU tests
  * that pin each one: INTEGRATION.md "Debug options"); MGICP_E_INVALID for an unknown name. */
 int mgicp_debug_option(mgicp_ctx* ctx, const char* name, double value);
 /* target cache (mgicp_release_cache): out[0] the current target was adopted from the cache, out[1]

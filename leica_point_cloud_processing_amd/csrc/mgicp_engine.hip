@@ -41,7 +41,18 @@ constexpr double kDefaultOccupancy = 10.0;          // mean points per non-empty
 constexpr size_t kSmallBytes = size_t(64) << 10;  // pinned readback scratch per context
 constexpr size_t kSketchOffset = size_t(32) << 10;  // the grid sizing sketch's registers in it (16 KiB)
 constexpr size_t kMaxCells = size_t(1) << 29;       // dense cell table cap (2 GiB of uint32)
-constexpr size_t kMaxBoxCells = size_t(1) << 27;    // per-cell point boxes up to 4 GiB (32 B per cell)
+// objective-pass launch shape over the fixed reduction tree, A/B-measured on MI355X at 5M points
+// (profiles/r02/ab_tree): 512 persistent 4-wave blocks -- 2 waves per SIMD, so chunk reductions
+// and tickets overlap other waves' streaming (71 us vs 76 us at 256 blocks), and the gated
+// grid (134 VGPRs: 3 waves per SIMD) stays resident while it waits at the gate (14.5 ms per C4
+// align vs 14.9 ms at 1024 blocks); in-launch finish
+constexpr int kFdfMaxBlocks = 512;
+// objective-pass event sampling while profiling: every 8th launch (identical work per launch, and two
+// event records per pass would cost ~4 % of the PCL-mode align)
+constexpr unsigned kProfStride = 8;
+// rings the lazy source's head-start k-NN searches before leaving a point to the lazy pass (caps 2-4
+// measured equal with the wave-per-point lazy pass, profiles/r06)
+constexpr int kAsyncRingCap = 4;
 
 double now_ms() {
   return std::chrono::duration<double, std::milli>(
@@ -49,9 +60,6 @@ double now_ms() {
       .count();
 }
 
-#ifndef MGICP_ASYNC_RING_CAP
-#define MGICP_ASYNC_RING_CAP 4  // rings the lazy source's head-start k-NN searches before leaving a point to the lazy pass
-#endif
 #ifndef MGICP_PASS_DIAG
 #define MGICP_PASS_DIAG 0
 #endif
@@ -265,12 +273,8 @@ struct Cloud {
   bool want_empty_map = false;
   DevBuf<uint32_t> seed, seed_scratch;  // seed map (target: first-sweep 1-NN seeds)
   bool want_seed_map = false;
-  DevBuf<float4> boxes;       // per-cell point boxes (target only: the 1-NN sweeps prune by them)
-  bool want_boxes = false;
   DevBuf<float4> pairs;       // pair-interleaved points (target only: the wave-uniform 1-NN scan)
-  bool want_pairs = false;
   bool drop_nonfinite = false; // build the grid over the finite points only (KdTreeFLANN semantics)
-  double occupancy = 0;        // grid sizing target (points per non-empty cell); 0 = context default
   size_t n_built = 0;          // points of the last grid built in this slot
   bool fresh_grid = false;     // the grid is the one a fresh context builds for these points (target cache)
   DevBuf<double2> cov;        // 3 * cov_stride
@@ -314,8 +318,7 @@ struct TargetCache {
   bool valid = false;
   Cloud t;
   int k = 0;
-  double eps = 0, occupancy = 0;
-  float vlist_cell = 0.f;
+  double eps = 0;
   bool vl_valid = false, vl_alloc = false, vl_off = false;
   VListView vl{};
   size_t vl_ncells = 0;
@@ -332,7 +335,7 @@ TargetCache g_tcache[64];
 template <class F>
 void each_target_buf(Cloud& a, Cloud& b, F&& f) {
   f(a.orig, b.orig); f(a.pts, b.pts); f(a.perm, b.perm); f(a.cell_start, b.cell_start);
-  f(a.empty_dist, b.empty_dist); f(a.seed, b.seed); f(a.seed_scratch, b.seed_scratch); f(a.boxes, b.boxes);
+  f(a.empty_dist, b.empty_dist); f(a.seed, b.seed); f(a.seed_scratch, b.seed_scratch);
   f(a.pairs, b.pairs); f(a.cov, b.cov);
 }
 void tcache_clear_locked(TargetCache& c) {
@@ -372,18 +375,7 @@ struct mgicp_ctx {
   DevBuf<float4> f_vox, f_vox2;
   DevBuf<unsigned char> f_keep;
   DevBuf<unsigned int> f_count;
-  double occupancy = kDefaultOccupancy;  // grid cell sizing target (debug option "grid_occ")
-  // objective-pass launch shape over the fixed reduction tree, A/B-measured on MI355X at 5M points
-  // (profiles/r02/ab_tree): 512 persistent 4-wave blocks -- 2 waves per SIMD, so chunk reductions
-  // and tickets overlap other waves' streaming (71 us vs 76 us at 256 blocks), and the gated
-  // grid (134 VGPRs: 3 waves per SIMD) stays resident while it waits at the gate (14.5 ms per C4
-  // align vs 14.9 ms at 1024 blocks); in-launch finish
   bool fused_finish = true;              // in-launch reduction finish (debug option "fused_finish")
-  int fdf_max_blocks = 512;              // objective-pass grid cap (fixed)
-  // alternate the objective-pass direction: 360 MB of streams at 5M points exceed the 256 MiB
-  // Infinity Cache, so each pass re-reads the previous pass's tail from it (73 -> 68 us)
-  bool alt_sweep = true;                 // (fixed)
-  int fdf_diag = 0;  // timing diagnostics of the objective pass (kernel modes 2 no reduction, 4 no tickets; not set by the host)
   double ms_upload_pending = 0;
   // host uploads go through the process-wide HostUploader (host_upload.hpp)
   int host_threads = 8;                  // packing workers (fixed)
@@ -394,15 +386,12 @@ struct mgicp_ctx {
   // compacted accepted correspondences of the current outer iteration (shard-relative)
   DevBuf<uint32_t> prev_pos;  // matched target sorted position per shard point (also the next 1-NN seed)
   DevBuf<uint32_t> flags;
-  DevBuf<unsigned char> nn_work;      // NnWork list of the wave sweep's stragglers (r03)
-  DevBuf<unsigned int> nn_work_n;
   DevBuf<float> corr_f;    // 6 streams
   DevBuf<double> corr_d;   // 6 streams
 
   size_t corr_cap = 0;     // elements per stream (multiple of 4)
   bool seed_valid = false;
   // query order of the 1-NN sweeps (Morton order of the shard)
-  bool query_order = true;
   bool qperm_valid = false;
   DevBuf<uint32_t> qperm;
   // the fixed reduction tree (internal.hpp kChunkPts / kSuperChunks): chunk layout of the streams,
@@ -411,7 +400,6 @@ struct mgicp_ctx {
   DevBuf<double> partial;       // chunk partials, kRedVals each
   DevBuf<unsigned long long> tpart;  // the server's stamped chunk partials, 32 words each (r03; 0xff.. = no stamp)
   size_t tpart_n = 0;
-  bool srv_tagged = true;            // the server's tagged tail (the chunk-ticket tail of r02 is the launched kernel's)
   DevBuf<double> spart;         // super partials (max_supers() rows: the all-gather send size)
   DevBuf<double> gath;          // nranks x max_supers() rows
   DevBuf<double> red;           // kRedVals
@@ -428,7 +416,6 @@ struct mgicp_ctx {
   unsigned long long* h_flag = nullptr;  // pass-completion word (host / device views)
   unsigned long long* d_flag = nullptr;
   unsigned long long pass_seq = 0;
-  bool poll = true;          // poll the completion word instead of hipStreamSynchronize (fixed)
   // pre-launched (gated) objective passes: pass k + 1 is queued while pass k runs and waits on the
   // host-written command block (debug option "gated"; single-GPU polled mode)
   bool gated = true;
@@ -439,11 +426,7 @@ struct mgicp_ctx {
   // BAR (debug option "bar_cmd"): every server block polls it, no PCIe read and no mailbox hop
   bool bar = true;
   PassCmd* bar_cmd = nullptr;
-  // blocks polling the host copy (fixed): 1 measured best (14.15 ms / C4 align;
-  // 8 pollers 14.8 ms, all 256 blocks on host memory ~70 ms: PCIe read contention;
-  // profiles/r02/ab_gate)
-  int gate_pollers = 1;
-  // MGICP_GATE_TRACE=1: per gated pass (seq & 1023) the device wall clock at kernel start, command
+  // MGICP_PASS_DIAG builds: per gated pass (seq & 1023) the device wall clock at kernel start, command
   // seen, last block through the gate; the host's wall clock (us) at flag seen / command published
   unsigned long long* h_gtrace = nullptr;  // mapped host memory, 4 x 1024
   unsigned long long* d_gtrace = nullptr;
@@ -460,26 +443,15 @@ struct mgicp_ctx {
   unsigned long long srv_next = 0;
   int cus = 0;                          // compute units (the server's grid)
   int srv_cus = 0;                      // debug option "srv_cus": cap on the server's blocks (0 = every CU)
-  int srv_waves = 4;                    // server shape: 4 waves per CU (one per SIMD)
   int stall_pass = -1;                  // env MGICP_SRV_STALL_PASS (tests): a server block withholds this pass
   int quit_pass = -1;                   // env MGICP_DEBUG_QUIT_PASS (tests): the host gives up at this pass index
                                         // with MGICP_E_COMM (a rank that dies mid-align, seen from the others)
-  bool corr_wave = true;                // wave-uniform 1-NN sweeps (fixed)
-  int corr_lds_pts = -1;                // small-ball waves: union-box cell bounds in LDS (-1), + points when <= N fit (N > 0), off (0) (MGICP_CORR_LDS_PTS)
-  int corr_split = 0;                   // waves of the wave sweep with <= this many stragglers hand them to a kernel of
-                                        // their own (MGICP_CORR_SPLIT; 0 = every straggler finishes in place)
-  float corr_rcap = 5.f;                // cells: lanes with a larger seed bound search alone (MGICP_CORR_RCAP)
-  // r03 A/B (profiles/r03/corrsweep): union boxes of <= 96 rows and 16 cells along x, for waves whose
-  // mean seed bound is >= 1.25 cells (the first sweep mostly): 2455 -> 2300 us per C4 align's sweeps
-  int corr_max_rows = 96;               // union boxes with more rows / x cells: per-lane search
-  int corr_max_x = 16;
-  float corr_union_min_r = 1.25f;       // cells: waves whose mean seed bound is smaller search per lane
   double row_deadline_ms = 500.0;       // env MGICP_ROW_DEADLINE_MS: own rows missing this long -> take over
   double remote_deadline_s = 120.0;     // env MGICP_REMOTE_DEADLINE_S: other ranks' rows / gathers
-  unsigned long long* h_ptimes = nullptr;  // MGICP_PASS_TIMES=1: per pass gate exit / finish (wall clock)
+  unsigned long long* h_ptimes = nullptr;  // MGICP_PASS_DIAG builds: per pass gate exit / finish (wall clock)
   unsigned long long* d_ptimes = nullptr;
-  // the passes' super partials as stamped host rows (32 words per super, two parity buffers; env
-  // MGICP_HOST_ROWS): private pinned memory, or the node-wide shared segment
+  // the passes' super partials as stamped host rows (32 words per super, two parity buffers; debug
+  // option "host_rows"): private pinned memory, or the node-wide shared segment
   bool host_rows = true;
   unsigned long long* h_rows = nullptr;
   unsigned long long* d_rows = nullptr;
@@ -513,8 +485,7 @@ struct mgicp_ctx {
   std::vector<SrvEv> srv_ev;            // launches not yet resolved (the last one may be live)
   double srv_time_ms = 0;
   long long srv_time_passes = 0, srv_time_launches = 0;
-  bool spin_pause = false;              // pause instruction in the row spin (off: measured no gain)
-  // MGICP_PASS_TIMES: host view of the server passes -- command published -> rows complete
+  // MGICP_PASS_DIAG builds: host view of the server passes -- command published -> rows complete
   // (device pass + PCIe both ways) and rows complete -> next command (host BFGS step)
   double ht_dev = 0, ht_host = 0, ht_bfgs = 0, ht_eval = 0, ht_last_rows = 0;
   int ht_n = 0, ht_nh = 0, ht_ne = 0;
@@ -522,7 +493,6 @@ struct mgicp_ctx {
   DevBuf<uint32_t> counts, keys, keys_sorted, vals;
   DevBuf<unsigned char> scratch;
   DevBuf<unsigned long long> u64;
-  bool split_target_cov = true;     // multi-GPU: target covariances split + all-gathered (fixed)
   // lazy source covariances (r04, debug option "lazy_src_cov"): a source point's covariance is computed the
   // first time a sweep accepts it -- every consumer (Mahalanobis of the compaction, GN moments) reads
   // accepted points only, so points the gate never accepts (clutter, debris far off the part) never
@@ -534,18 +504,16 @@ struct mgicp_ctx {
   DevBuf<uint32_t> cov_need;        // this sweep's accepted points without a covariance (absolute positions)
   // r04: set_target builds the target's grid and starts its k-NN covariances on a second stream, so
   // they run while the caller uploads the source; prepare joins them (debug option "async_cov" 0: off)
-  bool async_tgt = true;
-  // MGICP_AUX_CU_SKIP=k > 1: the aux stream on a CU mask leaving every k-th CU to the main stream (A/B
-  // 0, 2, 4, 8: profiles/r04/ncab1, up to -1.4 ms new clouds).  Off: a CU mask belongs to the hardware
-  // queue, and past GPU_MAX_HW_QUEUES streams share queues, so another context's main stream could
-  // inherit the mask -- and a resident server needs every CU (it stalled test_inlaunch_finish_*)
-  int aux_cu_skip = 0;
   // (and set_source the source's: single rank, same stream; with the lazy source mode these cover
   // every point, computed while the first sweep runs)
+  // The aux stream carries no CU mask, though leaving every k-th CU to the main stream measured up to
+  // -1.4 ms on new clouds (profiles/r04/ncab1): a CU mask belongs to the hardware queue, and past
+  // GPU_MAX_HW_QUEUES streams share queues, so another context's main stream could inherit the mask --
+  // and a resident server needs every CU (it stalled test_inlaunch_finish_*)
+  bool async_tgt = true;
   bool tgt_cov_pending = false;     // the aux stream's covariance launches not joined yet
   bool src_cov_pending = false;
   bool src_async_lazy = false;      // the source's launch was ring-capped (lazy mode): the rest stays lazy
-  int async_ring_cap = MGICP_ASYNC_RING_CAP;  // rings the source's head start searches (lazy mode)
   // one stream for both clouds' launches: with a stream each the process exceeds its hardware queues
   // (GPU_MAX_HW_QUEUES, 4) and the main stream ends up sharing one with them (profiles/r04/prep7)
   hipStream_t aux_stream = nullptr;
@@ -566,7 +534,6 @@ struct mgicp_ctx {
   bool vlist = true;
   bool fuse_compact = true;           // r04: compaction fused into listed sweeps (debug option "fuse_compact")
   DevBuf<uint32_t> vl_defer;          // chunks a fused sweep deferred to the compaction launch
-  float vlist_cell = 0.6f;            // fine cell edge / the target grid's cell edge (fixed)
   bool vl_stats = false;              // debug option "vlist_stats": per-sweep list diagnostics on stderr
   bool vl_valid = false;              // lists belong to the current target grid and gate
   bool vl_alloc = false;              // their state words and pool are allocated and initialised
@@ -607,7 +574,6 @@ struct mgicp_ctx {
   int n_evals = 0;
   // profiling
   bool profiling = false;
-  unsigned prof_stride = 8;   // objective-pass event sampling (fixed)
   unsigned long long prof_tick = 0;
   struct EvPair { hipEvent_t a, b; int fam; };
   std::vector<EvPair> pending;
@@ -666,9 +632,8 @@ struct ProfScope {
   int fam;
   hipEvent_t a = nullptr;
   ProfScope(mgicp_ctx* c, int f) : ctx(c), fam(f) {
-    // objective passes are sampled (every prof_stride-th launch: identical work per launch, and
-    // two event records per pass would cost ~4 % of the PCL-mode align); the rest are all timed
-    if (ctx->profiling && (fam != kFamFdf || (ctx->prof_tick++ % ctx->prof_stride) == 0)) {
+    // objective passes are sampled (every kProfStride-th launch); the rest are all timed
+    if (ctx->profiling && (fam != kFamFdf || (ctx->prof_tick++ % kProfStride) == 0)) {
       a = ev_get(ctx);
       (void)hipEventRecord(a, ctx->stream);
     }
@@ -860,7 +825,7 @@ int cov_prep_async(mgicp_ctx* ctx, bool tgt) {
   // the source in the lazy mode: a ring-capped launch (a point whose 20 neighbours lie beyond the
   // cap -- scan clutter, debris -- is left to the lazy pass, which computes it only if a sweep accepts
   // it; r04 C4F: the uncapped head start spent ~40 ms on them); its points are marked in cov_ok
-  const bool capped = !tgt && ctx->lazy_src_cov && ctx->knn_logged && ctx->async_ring_cap >= 0;
+  const bool capped = !tgt && ctx->lazy_src_cov && ctx->knn_logged;
   // r06 fix: the flag belongs to the SOURCE's launch -- the target's head start (set_target after
   // set_source on a context whose old target let the source start first) must not clear it, or the
   // source's join would mark the points its capped launch gave up on as computed (stale covariances)
@@ -885,7 +850,7 @@ int cov_prep_async(mgicp_ctx* ctx, bool tgt) {
   // the source's Morton query order is sorted on the aux stream ahead of its k-NN, so the main stream stays
   // empty for set_target's upload (r05: queued behind a main-stream sort that shares the CUs with the k-NN,
   // the target's copies waited ~2 ms)
-  if (!tgt && ctx->query_order && !ctx->qperm_valid && !ctx->qperm_aux) {
+  if (!tgt && !ctx->qperm_valid && !ctx->qperm_aux) {
     const size_t p0 = ctx->shard_p0(), ns = ctx->shard_p1() - p0;
     if (ns > 0 && morton_perm(ctx, c, p0, ns, ctx->qperm, true)) {
       HIPCK(hipEventRecord(ctx->aux_ev[2], ctx->aux_stream));
@@ -896,12 +861,12 @@ int cov_prep_async(mgicp_ctx* ctx, bool tgt) {
   HIPCK(launch_knn_cov(c.view, ctx->prm.k, ctx->prm.gicp_eps, 0, c.n, c.cov3(), nullptr,
                        ctx->knn_logged ? (tgt ? ctx->knn_fb.p : ctx->knn_fb2.p) : nullptr,
                        ctx->knn_logged ? ctx->aux_cnt.p + (tgt ? 0 : 1) : nullptr, ctx->aux_stream,
-                       capped ? ctx->async_ring_cap : -1, capped ? ctx->cov_ok.p : nullptr,
+                       capped ? kAsyncRingCap : -1, capped ? ctx->cov_ok.p : nullptr,
                        ctx->knn_logged ? 2 * std::max(ctx->cus, 1) : 0, ctx->knn_wave));
   HIPCK(hipEventRecord(ctx->aux_ev[tgt ? 0 : 1], ctx->aux_stream));
   MGICP_TRACE_AT(tgt ? "head start: target k-NN queued" : "head start: source k-NN queued");
   (tgt ? ctx->tgt_cov_pending : ctx->src_cov_pending) = true;
-  if (int rc = build_grid_extras(ctx, c)) return rc;  // the target's empty / seed map, boxes, pairs
+  if (int rc = build_grid_extras(ctx, c)) return rc;  // the target's empty / seed map, pairs
   // r05: the source's 1-NN query order (a Morton sort of the shard) now, on the main stream beside the
   // covariances -- not inside the first align's loop
   if (!tgt && !ctx->qperm_aux) (void)query_perm(ctx);
@@ -991,10 +956,7 @@ void tcache_donate(mgicp_ctx* ctx, bool cov_complete) {
   c.t.cov_stride = t.cov_stride;
   c.t.want_empty_map = t.want_empty_map;
   c.t.want_seed_map = t.want_seed_map;
-  c.t.want_boxes = t.want_boxes;
-  c.t.want_pairs = t.want_pairs;
   c.t.drop_nonfinite = t.drop_nonfinite;
-  c.t.occupancy = t.occupancy;
   c.t.n_built = t.n_built;
   c.t.fresh_grid = true;
   std::memcpy(c.t.lo, t.lo, sizeof(t.lo));
@@ -1003,7 +965,6 @@ void tcache_donate(mgicp_ctx* ctx, bool cov_complete) {
   c.t.ncells = t.ncells;
   c.k = ctx->prm.k;
   c.eps = ctx->prm.gicp_eps;
-  c.occupancy = t.occupancy > 0 ? t.occupancy : ctx->occupancy;
   // the cell lists travel with the target once built (the donor ran 3+ aligns on it).  The list policy
   // itself does not go on across contexts: GICPState's engines run 2 aligns each, and building the lists
   // in a later cycle cost 39 + 151 ms at C4 (profiles/r05/check5) against ~1.6 ms saved per cycle
@@ -1020,7 +981,6 @@ void tcache_donate(mgicp_ctx* ctx, bool cov_complete) {
     c.vl_ncells = ctx->vl_ncells;
     c.vl_epoch = ctx->vl_epoch;
     c.vl_groups = ctx->vl_groups;
-    c.vlist_cell = ctx->vlist_cell;
   }
   c.valid = true;
   c.donations++;
@@ -1034,9 +994,7 @@ int tcache_adopt(mgicp_ctx* ctx) {
   if (!ctx->tcache_on || ctx->nranks != 1 || ctx->comm || ctx->have_shm) return MGICP_OK;
   TargetCache& c = g_tcache[ctx->device & 63];
   std::lock_guard<std::mutex> lk(c.mu);
-  const double occ = t.occupancy > 0 ? t.occupancy : ctx->occupancy;
-  if (!c.valid || c.t.n != t.n || c.occupancy != occ || c.t.drop_nonfinite != t.drop_nonfinite ||
-      c.t.want_pairs != t.want_pairs || c.t.want_boxes != t.want_boxes)
+  if (!c.valid || c.t.n != t.n || c.t.drop_nonfinite != t.drop_nonfinite)
     return MGICP_OK;
   unsigned int* diff = reinterpret_cast<unsigned int*>(ctx->d_small);
   MGICP_TRACE_AT("adopt: compare");
@@ -1060,7 +1018,7 @@ int tcache_adopt(mgicp_ctx* ctx) {
   t.view = c.t.view;  // the same device memory, now this context's
   t.ncells = c.t.ncells;
   ctx->vl_valid = false;
-  if (c.vl_valid && c.vlist_cell == ctx->vlist_cell) {
+  if (c.vl_valid) {
     if (c.vl_alloc) {
       swap_buf(ctx->vl_cell, c.vl_cell);
       swap_buf(ctx->vl_pool, c.vl_pool);
@@ -1148,7 +1106,7 @@ int build_grid(mgicp_ctx* ctx, Cloud& cl, bool defer_extras) {
     maxabs = std::max(maxabs, std::max(std::fabs(mn[d]), std::fabs(mx[d])));
   }
   // 2. cell size: aim at `target_occ` points per non-empty cell
-  const double target_occ = cl.occupancy > 0 ? cl.occupancy : ctx->occupancy;
+  const double target_occ = kDefaultOccupancy;
   auto dims = [&](double h, int* nd) {
     size_t nc = 1;
     for (int d = 0; d < 3; ++d) {
@@ -1234,7 +1192,7 @@ int build_grid(mgicp_ctx* ctx, Cloud& cl, bool defer_extras) {
   HIPCK(cl.cell_start.reserve(nc + 1));
   HIPCK(cl.pts.reserve(n));
   MGICP_TRACE_AT("grid: final buffers reserved");
-  HIPCK(launch_cell_hist(cl.orig.p, n, mn[0], mn[1], mn[2], inv_h, nd[0], nd[1], nd[2], nullptr, ctx->keys.p, s));
+  HIPCK(launch_cell_keys(cl.orig.p, n, mn[0], mn[1], mn[2], inv_h, nd[0], nd[1], nd[2], ctx->keys.p, s));
   int bits = 1;
   while ((size_t(1) << bits) < nc && bits < 32) ++bits;
   const size_t sb = std::max(sort_scratch_bytes(n, bits), cell_start_scratch_bytes(nc));
@@ -1276,7 +1234,6 @@ int build_grid(mgicp_ctx* ctx, Cloud& cl, bool defer_extras) {
   g.pts = cl.pts.p;
   g.empty_dist = nullptr;
   g.seed = nullptr;
-  g.boxes = nullptr;
   g.pairs = nullptr;
   cl.ncells = nc;
   cl.n_built = n;
@@ -1292,7 +1249,7 @@ int build_grid(mgicp_ctx* ctx, Cloud& cl, bool defer_extras) {
   return defer_extras ? MGICP_OK : build_grid_extras(ctx, cl);
 }
 
-// The 1-NN sweeps' extras of a built grid (target): empty-space + seed map, per-cell boxes, the
+// The 1-NN sweeps' extras of a built grid (target): empty-space + seed map, the
 // pair-interleaved copy -- queued on the main stream, no host wait.  r06: set_target's head start queues
 // the target's k-NN (which needs none of them) BEFORE these, so the 0.7-0.8 ms of the empty map at C4 run
 // beside the k-NN instead of in front of it (the target's k-NN is the cold first align's long pole).
@@ -1314,12 +1271,7 @@ int build_grid_extras(mgicp_ctx* ctx, Cloud& cl) {
     g.empty_dist = cl.empty_dist.p;
     if (cl.want_seed_map) g.seed = cl.seed.p;
   }
-  if (cl.want_boxes && nc <= kMaxBoxCells) {
-    HIPCK(cl.boxes.reserve(2 * nc));
-    HIPCK(launch_cell_boxes(cl.pts.p, cl.cell_start.p, nc, cl.boxes.p, s));
-    g.boxes = cl.boxes.p;
-  }
-  if (cl.want_pairs) {
+  if (&cl == &ctx->tgt) {  // the wave-uniform 1-NN scan reads the target's pair copy
     HIPCK(cl.pairs.reserve(2 * pair_count(n)));
     HIPCK(launch_pairs(cl.pts.p, n, cl.pairs.p, s));
     g.pairs = cl.pairs.p;
@@ -1350,7 +1302,6 @@ bool morton_perm(mgicp_ctx* ctx, const Cloud& c, size_t p0, size_t n, DevBuf<uin
 
 // query order of the shard's 1-NN sweeps and source covariances (once per source cloud and shard)
 const uint32_t* query_perm(mgicp_ctx* ctx) {
-  if (!ctx->query_order) return nullptr;
   if (ctx->qperm_aux) {  // sorted on the aux stream at set_source: the main stream waits for it on the device
     ctx->qperm_aux = false;
     if (hipStreamWaitEvent(ctx->stream, ctx->aux_ev[2], 0) != hipSuccess) ctx->qperm_valid = false;
@@ -1439,7 +1390,7 @@ int compute_cov(mgicp_ctx* ctx, Cloud& cl, size_t p0, size_t p1, size_t stride =
 // per point, so the result is the single-GPU one bit for bit.
 int target_cov(mgicp_ctx* ctx) {
   Cloud& t = ctx->tgt;
-  if (!ctx->comm || ctx->nranks < 2 || !ctx->split_target_cov) return compute_cov(ctx, t, 0, t.n);
+  if (!ctx->comm || ctx->nranks < 2) return compute_cov(ctx, t, 0, t.n);
   const size_t N = static_cast<size_t>(ctx->nranks), r = static_cast<size_t>(ctx->rank);
   const size_t cnt = (t.n + N - 1) / N;
   int rc = compute_cov(ctx, t, std::min(t.n, r * cnt), std::min(t.n, (r + 1) * cnt), N * cnt);
@@ -1683,7 +1634,7 @@ int take_over(mgicp_ctx* ctx, unsigned int rstamp, const Xf34& A) {
   ctx->st[kStLaunchedPass]++;
   const size_t ns = ctx->shard_p1() - ctx->shard_p0();
   HIPCK(launch_fdf_soa(corr_soa(ctx), ctx->ccnt.p, ns, A, ctx->partial.p, ctx->spart.p,
-                       fdf_grid_blocks(ns, ctx->fdf_max_blocks), ctx->tickets.p, nullptr, 0, nullptr, 0, ctx->stream,
+                       fdf_grid_blocks(ns, kFdfMaxBlocks), ctx->tickets.p, nullptr, 0, nullptr, 0, ctx->stream,
                        row_view(ctx).dev_rows(rstamp), rstamp));
   // host-row passes leave the tickets as multiples of their supers' sizes: re-arm them for whatever
   // form the next pass takes
@@ -1706,7 +1657,6 @@ int wait_rows(mgicp_ctx* ctx, unsigned int rstamp, const Xf34& A, double out[kRe
   auto wait_row = [&](long long r, bool own) -> int {
     const unsigned long long* row = buf + shm::kRowWords * static_cast<size_t>(r);
     for (unsigned spins = 0; !shm::row_complete(reinterpret_cast<const uint64_t*>(row), rstamp); ++spins) {
-      if (ctx->spin_pause) __builtin_ia32_pause();
       if ((spins & 1023u) != 1023u) continue;
       const double el = shm::elapsed_s(t0);
       if (own && !taken && allow_takeover && el > dl_own) {
@@ -1897,8 +1847,9 @@ CorrSoA corr_soa(mgicp_ctx* ctx) {
 // The fine grid of the target's 1-NN cell lists for the current gate (once per target grid and gate;
 // the lists themselves are built by the sweeps, cell by cell, the first time a query lands in a cell).
 // The grid covers the target's bbox grown by the gate + 2 cells, so a query outside it is farther than
-// the gate from every target point; cells of vlist_cell x the target grid's cell edge, fewer than 2^28
+// the gate from every target point; cells of kVlistCell x the target grid's cell edge, fewer than 2^28
 // cells (else the lists are off for this gate: the r03 sweeps).
+constexpr double kVlistCell = 0.6f;  // fine cell edge / the target grid's cell edge (the float 0.6f, widened)
 int vl_prepare(mgicp_ctx* ctx) {
   const double gate = ctx->prm.max_corr_dist;
   const size_t ns = ctx->shard_p1() - ctx->shard_p0();
@@ -1907,7 +1858,7 @@ int vl_prepare(mgicp_ctx* ctx) {
     ctx->vl_off = false;
     const Cloud& t = ctx->tgt;
     const double h = t.view.h;
-    double c = std::max(h * static_cast<double>(ctx->vlist_cell), 1e-6);
+    double c = std::max(h * kVlistCell, 1e-6);
     double ext = 0, maxabs = 0;
     for (int d = 0; d < 3; ++d) {
       ext = std::max(ext, static_cast<double>(t.hi[d] - t.lo[d]));
@@ -2004,21 +1955,8 @@ hipError_t launch_sweep(mgicp_ctx* ctx, const Mat4& T, double thr, bool seeded, 
   if (sweep_listed(ctx))
     return launch_vl_sweep(g, ctx->vl, ctx->d_out, p0, p1, T.xf(), thr, seeded ? 1 : 0, ctx->prev_pos.p, ctx->flags.p,
                            ctx->cus, ctx->stream, fc);
-  if (ctx->corr_wave && g.pairs) {
-    const float rc = ctx->corr_rcap * g.h;
-    void* work = nullptr;
-    if (ctx->corr_split > 0) {
-      hipError_t e = ctx->nn_work.reserve(nn_work_bytes(p1 - p0));
-      if (e == hipSuccess) e = ctx->nn_work_n.reserve(1);
-      if (e != hipSuccess) return e;
-      work = ctx->nn_work.p;
-    }
-    return launch_correspond_wave(g, ctx->d_out, p0, p1, T.xf(), thr, seeded ? 1 : 0, ctx->prev_pos.p,
-                                  ctx->flags.p, qp, rc * rc, ctx->corr_max_rows, ctx->corr_max_x, ctx->corr_union_min_r,
-                                  work, ctx->nn_work_n.p, ctx->corr_split, ctx->corr_lds_pts, ctx->stream);
-  }
-  return launch_correspond(g, ctx->d_out, p0, p1, T.xf(), thr, seeded ? 1 : 0, ctx->prev_pos.p, ctx->flags.p, qp,
-                           ctx->stream);
+  return launch_correspond_wave(g, ctx->d_out, p0, p1, T.xf(), thr, seeded ? 1 : 0, ctx->prev_pos.p, ctx->flags.p, qp,
+                                ctx->stream);
 }
 
 // One correspondence sweep (the loop body of computeTransformation before the BFGS call):
@@ -2111,16 +2049,11 @@ int correspond(mgicp_ctx* ctx, const Mat4& T, const Mat4& G, bool seed) {
     unsigned long long st[8];
     HIPCK(hipStreamSynchronize(s));
     HIPCK(corr_stats_take(st));
-    if (ctx->corr_wave && ctx->tgt.view.pairs)
-      std::fprintf(stderr, "[corr-stats] wave scan: queries %llu accepted %llu rejected %llu | per-lane tests/query %.1f "
-                   "ranges/query %.1f | lanes left to the per-lane search %llu | union-scan waves %llu of %llu, "
-                   "candidates per union wave %.1f\n",
-                   st[0], st[1], st[2], st[0] ? double(st[3]) / st[0] : 0.0, st[0] ? double(st[4]) / st[0] : 0.0, st[5],
-                   st[7], (st[0] + 63) / 64, st[7] ? double(st[6]) / st[7] : 0.0);
-    else
-      std::fprintf(stderr, "[corr-stats] queries %llu accepted %llu rejected %llu | tests/query acc %.1f rej %.1f | ranges/query acc %.1f rej %.1f\n",
-                   st[0], st[1], st[2], st[1] ? double(st[3]) / st[1] : 0.0, st[2] ? double(st[4]) / st[2] : 0.0,
-                   st[1] ? double(st[5]) / st[1] : 0.0, st[2] ? double(st[6]) / st[2] : 0.0);
+    std::fprintf(stderr, "[corr-stats] wave scan: queries %llu accepted %llu rejected %llu | per-lane tests/query %.1f "
+                 "ranges/query %.1f | lanes left to the per-lane search %llu | union-scan waves %llu of %llu, "
+                 "candidates per union wave %.1f\n",
+                 st[0], st[1], st[2], st[0] ? double(st[3]) / st[0] : 0.0, st[0] ? double(st[4]) / st[0] : 0.0, st[5],
+                 st[7], (st[0] + 63) / 64, st[7] ? double(st[6]) / st[7] : 0.0);
   }
 #endif
   {
@@ -2156,12 +2089,12 @@ struct DeviceFunctor {
     const double t_entry = ctx->h_ptimes ? now_ms() : 0.0;
     const Mat4 A = apply_state(x);
     const size_t ns = ctx->shard_p1() - ctx->shard_p0();
-    const int nb = fdf_grid_blocks(ns, ctx->fdf_max_blocks);
+    const int nb = fdf_grid_blocks(ns, kFdfMaxBlocks);
     int rc;
     // alternate the sweep direction so each pass starts on the Infinity-Cache-resident tail
-    // of the previous one (deterministic: the sums do not depend on the direction)
-    const int reverse = (ctx->alt_sweep ? (ctx->n_evals & 1) : 0) | ctx->fdf_diag;
-    const bool poll = ctx->poll && !ctx->fdf_diag;
+    // of the previous one (deterministic: the sums do not depend on the direction): 360 MB of
+    // streams at 5M points exceed the 256 MiB Infinity Cache (73 -> 68 us per pass)
+    const int reverse = ctx->n_evals & 1;
     // the pass's row stamp: the objective-pass index, identical on every rank (0 is never a stamp;
     // stamps >= 2^31 belong to mgicp_debug_pass_bench's timing form).  At the wrap every stamped
     // buffer is cleared and the count restarts at 1, so parity buffers keep alternating.
@@ -2178,14 +2111,13 @@ struct DeviceFunctor {
     const bool shm_rows = ctx->have_shm;
     const bool inlaunch = ctx->fused_finish && !ctx->comm && ctx->nranks == 1 && !shm_rows;
     double* out = inlaunch ? ctx->d_h_red : nullptr;
-    const bool gate = ctx->gated && poll && inlaunch && !ctx->profiling;
+    const bool gate = ctx->gated && inlaunch && !ctx->profiling;
     const Xf34 Ax = A.xf();
     const CorrSoA c = corr_soa(ctx);
-    const bool want_srv = ctx->resident && !ctx->srv_degraded && !ctx->profiling && !ctx->fdf_diag &&
-                          (gate || (shm_rows && ctx->poll));
+    const bool want_srv = ctx->resident && !ctx->srv_degraded && !ctx->profiling && (gate || shm_rows);
     int cap = ctx->srv_cus > 0 ? std::min(ctx->srv_cus, ctx->cus) : ctx->cus;
     if (ctx->have_xgmi) cap = std::min(cap, ctx->cus - 1);  // one CU left to the totaler wave
-    int nsrv = want_srv ? fdf_server_blocks(ns, cap, ctx->srv_waves) : 0;
+    int nsrv = want_srv ? fdf_server_blocks(ns, cap) : 0;
     // the host rows first: a failure here (e.g. a source larger than the shared segment) must not
     // leave the device's server slot taken
     if (!ctx->srv_live && (shm_rows || (nsrv > 0 && ctx->host_rows)) && (rc = ensure_rows(ctx))) return rc;
@@ -2226,8 +2158,8 @@ struct DeviceFunctor {
             e = launch_fdf_server(c, ctx->ccnt.p, ns, ctx->partial.p, ctx->spart.p, ctx->tickets.p,
                                   out, ctx->d_flag, seq, ctx->bar_cmd ? ctx->bar_cmd : ctx->d_cmd, ctx->mail,
                                   ctx->gate_timeout, ctx->d_ptimes, 0, Ax, xg ? xr : (rows ? rv.dev_rows(0) : nullptr),
-                                  rv.stride, nsrv, ctx->srv_waves, ctx->bar_cmd ? nsrv : 1, ctx->stall_pass,
-                                  ctx->srv_tagged ? ctx->tpart.p : nullptr, ctx->stream, xg ? &pr : nullptr);
+                                  rv.stride, nsrv, ctx->bar_cmd ? nsrv : 1, ctx->stall_pass, ctx->tpart.p, ctx->stream,
+                                  xg ? &pr : nullptr);
           // the totaler of this BFGS run (its own stream; exits on the generation change of the cancel)
           if (e == hipSuccess && xg) {
             const unsigned int gen = ++ctx->xgen;
@@ -2302,15 +2234,18 @@ struct DeviceFunctor {
       cancel_gated(ctx);
       ProfScope ps(ctx, kFamFdf);
       HIPCK(launch_fdf_soa(c, ctx->ccnt.p, ns, Ax, ctx->partial.p, ctx->spart.p, nb,
-                           ctx->tickets.p, out, reverse, (poll && inlaunch) ? ctx->d_flag : nullptr, seq,
+                           ctx->tickets.p, out, reverse, inlaunch ? ctx->d_flag : nullptr, seq,
                            ctx->stream));
     }
     if (gate) {
+      // blocks polling the host copy of the command: 1 measured best (14.15 ms / C4 align; 8 pollers
+      // 14.8 ms, all 256 blocks on host memory ~70 ms: PCIe read contention; profiles/r02/ab_gate)
+      constexpr int kGatePollers = 1;
       // queue pass seq + 1 now (its launch overlaps this pass); it runs once the BFGS step has
       // published x_{k+1}, or exits on cancel when the BFGS run ends
       HIPCK(launch_fdf_soa_gated(c, ctx->ccnt.p, ns, ctx->partial.p, ctx->spart.p, nb,
                                  ctx->tickets.p, out, ctx->d_flag, seq + 1, ctx->d_cmd, ctx->mail,
-                                 ctx->gate_timeout, ctx->d_gtrace, ctx->gate_pollers, ctx->stream));
+                                 ctx->gate_timeout, ctx->d_gtrace, kGatePollers, ctx->stream));
       ctx->gated_seq = seq + 1;
     }
     if (!inlaunch) {
@@ -2318,14 +2253,9 @@ struct DeviceFunctor {
         ProfScope ps(ctx, kFamRed);
         if ((rc = combine_supers(ctx, kRedVals, ctx->spart.p, ctx->red.p))) return rc;
       }
-      if (poll) {
-        HIPCK(launch_publish(ctx->red.p, kRedVals, ctx->d_h_red, ctx->d_flag, seq, ctx->stream));
-      } else {
-        HIPCK(hipMemcpyAsync(ctx->h_red, ctx->red.p, kRedVals * sizeof(double), hipMemcpyDeviceToHost,
-                             ctx->stream));
-      }
+      HIPCK(launch_publish(ctx->red.p, kRedVals, ctx->d_h_red, ctx->d_flag, seq, ctx->stream));
     }
-    rc = poll ? wait_pass(ctx, seq) : sync(ctx);
+    rc = wait_pass(ctx, seq);
     if (ctx->h_gtrace) ctx->host_gt[2 * ((seq + 1) & 1023)] = now_ms() * 1e3;  // sums of seq seen
     if (rc) return rc;
     std::memcpy(sums, ctx->h_red, kRedVals * sizeof(double));
@@ -2597,11 +2527,6 @@ int mgicp_create(mgicp_ctx** out, const mgicp_params* p) {
     ctx->cus = 0;  // no resident server
   ctx->tgt.want_empty_map = true;  // correspondence / fitness queries start off the surface
   ctx->tgt.want_seed_map = true;  // first 1-NN sweep seeded from a nearest non-empty cell
-  // per-cell point boxes in the 1-NN sweeps: exact and 1.75x fewer candidates in sweep 1, but the
-  // per-cell box loads and tests cost more than they save (C4 correspondence 1.39 vs 1.11 ms,
-  // profiles/r02/ab_boxes): off
-  ctx->tgt.want_boxes = false;
-  ctx->tgt.want_pairs = ctx->corr_wave;  // the wave-uniform 1-NN scan (r03) reads the target's pair copy
   if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) {
     delete ctx;
     return MGICP_E_HIP;
@@ -2681,7 +2606,7 @@ void mgicp_destroy(mgicp_ctx* ctx) {
   ctx->f_count.release();
   for (Cloud* c : {&ctx->src, &ctx->tgt, &ctx->aux, &ctx->qry}) {
     c->raw.release(); c->orig.release(); c->pts.release(); c->perm.release();
-    c->cell_start.release(); c->cov.release(); c->empty_dist.release(); c->boxes.release(); c->pairs.release();
+    c->cell_start.release(); c->cov.release(); c->empty_dist.release(); c->pairs.release();
     c->seed.release(); c->seed_scratch.release();
   }
   ctx->src_out.release();
@@ -2695,7 +2620,6 @@ void mgicp_destroy(mgicp_ctx* ctx) {
   ctx->tickets_n = 0;
   ctx->ccnt.release(); ctx->spart.release(); ctx->gath.release(); ctx->msuper.release();
   ctx->prev_pos.release(); ctx->flags.release();
-  ctx->nn_work.release(); ctx->nn_work_n.release();
   ctx->vl_cell.release(); ctx->vl_pool.release(); ctx->vl_ctr.release();
   ctx->vl_build.release(); ctx->vl_bcentre.release(); ctx->vl_pend.release(); ctx->vl_defer.release();
   ctx->cov_ok.release(); ctx->cov_need.release();
@@ -3570,7 +3494,7 @@ int mgicp_debug_pass_bench(mgicp_ctx* ctx, const double x[6], int npasses, int m
   if (rows) HIPCK(hipMemsetAsync(ctx->tickets.p, 0, ctx->tickets_n * sizeof(unsigned int), ctx->stream));
   if (mode == 0) {
     const int cap = ctx->srv_cus > 0 ? std::min(ctx->srv_cus, ctx->cus) : ctx->cus;
-    const int nb = fdf_server_blocks(ns, cap, ctx->srv_waves);
+    const int nb = fdf_server_blocks(ns, cap);
     if (nb <= 0) {
       (void)hipEventDestroy(a);
       (void)hipEventDestroy(b);
@@ -3580,14 +3504,13 @@ int mgicp_debug_pass_bench(mgicp_ctx* ctx, const double x[6], int npasses, int m
     const RowView rv = row_view(ctx);
     e = launch_fdf_server(c, ctx->ccnt.p, ns, ctx->partial.p, ctx->spart.p, ctx->tickets.p,
                           ctx->d_h_red, ctx->d_flag, seq0, ctx->d_cmd, ctx->mail, ctx->gate_timeout, ctx->d_ptimes,
-                          npasses, A, rows ? rv.dev_rows(0) : nullptr, rv.stride, nb, ctx->srv_waves, 1, -1,
-                          ctx->srv_tagged ? ctx->tpart.p : nullptr, ctx->stream);
+                          npasses, A, rows ? rv.dev_rows(0) : nullptr, rv.stride, nb, 1, -1, ctx->tpart.p, ctx->stream);
     ctx->pass_seq = seq0 + static_cast<unsigned long long>(npasses);  // the closing cancel's stamp too
   } else {
-    const int nb = fdf_grid_blocks(ns, ctx->fdf_max_blocks);
+    const int nb = fdf_grid_blocks(ns, kFdfMaxBlocks);
     for (int k = 0; k < npasses && e == hipSuccess; ++k)
       e = launch_fdf_soa(c, ctx->ccnt.p, ns, A, ctx->partial.p, ctx->spart.p, nb, ctx->tickets.p,
-                         ctx->d_h_red, ctx->alt_sweep ? (k & 1) : 0, ctx->d_flag, ++ctx->pass_seq, ctx->stream);
+                         ctx->d_h_red, k & 1, ctx->d_flag, ++ctx->pass_seq, ctx->stream);
   }
   if (e == hipSuccess) e = hipEventRecord(b, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
@@ -3654,7 +3577,7 @@ int mgicp_debug_supers(mgicp_ctx* ctx, int kind, const double* arg, double* out,
     // host-row passes leave the tickets as multiples of their supers' sizes
     HIPCK(hipMemsetAsync(ctx->tickets.p, 0, ctx->tickets_n * sizeof(unsigned int), ctx->stream));
     HIPCK(launch_fdf_soa(corr_soa(ctx), ctx->ccnt.p, ns, apply_state(x).xf(), ctx->partial.p,
-                         ctx->spart.p, fdf_grid_blocks(ns, ctx->fdf_max_blocks), ctx->tickets.p, nullptr, 0,
+                         ctx->spart.p, fdf_grid_blocks(ns, kFdfMaxBlocks), ctx->tickets.p, nullptr, 0,
                          nullptr, 0, ctx->stream));
   } else if (kind == 1) {
     if (!ctx->seed_valid) return fail(ctx, MGICP_E_INVALID, "no correspondence sweep yet");
@@ -3794,8 +3717,6 @@ int mgicp_debug_option(mgicp_ctx* ctx, const char* name, double value) {
     ctx->lazy_src_cov = on;
     ctx->src.have_cov = false;
     ctx->src_lazy_ready = false;
-  } else if (n == "async_ring_cap") {                   // rings the source's lazy-mode head start searches (-1: all)
-    ctx->async_ring_cap = iv;
   } else if (n == "knn_wave") {                         // k-NN: lazy pass + hand-offs one wave per point (1) or per lane (0)
     ctx->knn_wave = on;
   } else if (n == "knn_logged") {                       // k-NN: the logged kernel + hand-off (1) or the register-list kernel only (0)
@@ -3808,10 +3729,7 @@ int mgicp_debug_option(mgicp_ctx* ctx, const char* name, double value) {
   else if (n == "vlist_stats") ctx->vl_stats = on;      // per-sweep list statistics on stderr
   else if (n == "fuse_compact") ctx->fuse_compact = on; // compaction fused into listed sweeps
   else if (n == "target_cache") ctx->tcache_on = on;    // adopt / leave the target state (process cache)
-  else if (n == "grid_occ") {                           // grid sizing (points per non-empty cell), next set_*
-    if (!(value >= 1.0 && value <= 256.0)) return fail(ctx, MGICP_E_INVALID, "grid_occ must be in [1, 256]");
-    ctx->occupancy = value;
-  } else if (n == "bar_cmd") {                          // server commands through the BAR (else pinned copy)
+  else if (n == "bar_cmd") {                            // server commands through the BAR (else pinned copy)
     ctx->bar = on;
     if (!on && ctx->bar_cmd) {
       (void)hipFree(ctx->bar_cmd);

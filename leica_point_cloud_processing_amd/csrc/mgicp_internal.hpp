@@ -30,9 +30,6 @@ struct GridView {
   // optional seed map (with empty_dist): per cell within the cap, the sorted position of a point in
   // a Chebyshev-nearest non-empty cell -- a real candidate that seeds an unseeded 1-NN search
   const uint32_t* seed;
-  // optional per-cell point boxes (2 float4 per cell: min xyz | bits(start), max xyz | bits(end));
-  // 1-NN searches skip cells whose point box lies beyond their bound
-  const float4* boxes;
   // optional pair-interleaved copy of pts for the wave-uniform 1-NN scan (2 float4 per pair of
   // points: x0 x1 y0 y1 | z0 z1 w0 w1; pair_count(n) pairs, far sentinels past n)
   const float4* pairs;
@@ -110,9 +107,9 @@ hipError_t launch_pack_points(const void* raw, size_t n, size_t stride, float4* 
                               hipStream_t s);
 hipError_t launch_bbox(const float4* pts, size_t n, float* partial /*nb*8*/, int nb,
                        hipStream_t s);
-hipError_t launch_cell_hist(const float4* pts, size_t n, float ox, float oy, float oz,
-                            float inv_h, int nx, int ny, int nz, uint32_t* counts,
-                            uint32_t* keys /*nullable*/, hipStream_t s);
+// linear cell index (z-major) of every point: the keys of the grid's sort
+hipError_t launch_cell_keys(const float4* pts, size_t n, float ox, float oy, float oz,
+                            float inv_h, int nx, int ny, int nz, uint32_t* keys, hipStream_t s);
 // r06: the grid's sizing sketch (cell_sketch_kernel): kSketchR one-byte HyperLogLog registers of the
 // occupied cells at each of kSketchScales cell sizes (1 / inv[k]) over origin (ox, oy, oz), in one pass;
 // `partial` holds (kSketchBlocks + 32) * kSketchScales * kSketchR bytes, the merged registers land in `out`
@@ -149,20 +146,11 @@ hipError_t launch_knn_cov(const GridView& g, int k, double eps, size_t p0, size_
                           bool wave_handoff = true /*r06: the chained hand-off by knn_wave_kernel*/);
 // nn_pos: per source point (shard-relative) the matched target sorted position, UINT32_MAX when
 // rejected; with `seeded` its previous contents seed the exact 1-NN search.  flags: 1 if accepted.
-hipError_t launch_correspond(const GridView& tgt, const float4* src, size_t p0, size_t p1, Xf34 T,
-                             double thr, int seeded, uint32_t* nn_pos, uint32_t* flags,
-                             const uint32_t* qperm /*nullable: query order*/, hipStream_t s);
-// the wave-uniform form (needs tgt.pairs): lanes whose seed bound exceeds sqrt(rcap2), or waves whose
-// union box exceeds max_rows rows or max_xcells cells along x, or whose mean seed bound is below
-// union_min_r cells, finish with the per-lane search
+// The wave-uniform 1-NN sweep (needs tgt.pairs); lanes the union scan does not settle finish with the
+// per-lane search (limits: mgicp_kernels.hip, launch_correspond_wave)
 hipError_t launch_correspond_wave(const GridView& tgt, const float4* src, size_t p0, size_t p1, Xf34 T,
-                                  double thr, int seeded, uint32_t* nn_pos, uint32_t* flags, const uint32_t* qperm,
-                                  float rcap2, int max_rows, int max_xcells, float union_min_r,
-                                  void* work /*nullable: NnWork list of stragglers, nn_work_bytes(p1 - p0)*/,
-                                  unsigned int* work_n, int split_max /*waves with at most this many stragglers hand them on*/,
-                                  int lds_cap /*small-ball waves: union box staged in LDS when it has <= lds_cap points*/,
-                                  hipStream_t s);
-size_t nn_work_bytes(size_t n);
+                                  double thr, int seeded, uint32_t* nn_pos, uint32_t* flags,
+                                  const uint32_t* qperm /*nullable: query order*/, hipStream_t s);
 
 // ---- the target's 1-NN cell lists (r04; DESIGN.md "1-NN cell lists") ----
 // A fine uniform grid over the target's bbox grown by the gate.  Per cell: the target points that can
@@ -201,7 +189,7 @@ struct VListView {
 };
 // one sweep over the lists: listed queries answered at once, reject cells rejected, the others
 // queued (pend) and their cells requested; then the requested cells' lists are built and the
-// pending queries answered by the exact per-lane search (seeded like correspond_kernel)
+// pending queries answered by the exact per-lane search (seeded like correspond_wave_kernel's)
 // the compaction fused into a listed sweep (vl_query_compact_kernel): its inputs; chunks it cannot
 // finish (a pending query, a lazy source covariance not computed yet) are listed in `defer`, count
 // in VListView::ctr[3], for launch_compact(..., defer, ctr + 3)
@@ -260,7 +248,7 @@ int        fdf_grid_blocks(size_t ns, int max_blocks = 2048);
 // ... each run on the command with that stamp, until a cancel (or a later command); bench_passes > 0
 // (timing): that many passes of A back to back without commands.  fdf_server_blocks: its grid for a
 // shard of ns positions on `cus` CUs (0: not servable, use the launched passes)
-int        fdf_server_blocks(size_t ns, int cus, int waves /*4 per CU*/);
+int        fdf_server_blocks(size_t ns, int cus);
 // r05, N > 1 over xGMI: the other ranks' exchange buffers (IPC-mapped device memory), at this rank's
 // first super; a super's reducer stores its row into its own buffer (host_rows) and into every one of
 // these, so each rank's buffer receives every rank's rows
@@ -276,7 +264,7 @@ hipError_t launch_fdf_server(const CorrSoA& c, const uint32_t* ccnt, size_t ns, 
                              int bench_passes, Xf34 A,
                              unsigned long long* host_rows /*nullable: super rows to the host, parity 0*/,
                              size_t rows_stride /*words from the parity-0 to the parity-1 row buffer*/, int nb,
-                             int waves, int pollers /*blocks reading cmd themselves (1 or nb)*/,
+                             int pollers /*blocks reading cmd themselves (1 or nb)*/,
                              int stall_pass /*tests: -1, or the pass the last block withholds*/,
                              unsigned long long* tpart /*nullable: stamped chunk partials, 32 words per chunk (r03)*/,
                              hipStream_t s, const PeerRows* peers = nullptr);
@@ -355,9 +343,6 @@ hipError_t launch_equal(const float4* a, const float4* b, size_t n, unsigned int
 // resolve all kernels once (moves the code-object loading cost into mgicp_create)
 // and exercise both copy directions once, small and large (pinned: pinned host scratch)
 hipError_t preload_kernels(void* pinned, size_t pinned_bytes, hipStream_t s);
-// per-cell point boxes of a built grid (GridView::boxes), 2 * nc float4
-hipError_t launch_cell_boxes(const float4* pts, const uint32_t* cell_start, size_t nc, float4* boxes,
-                             hipStream_t s);
 // empty-space distance map of a grid (3 separable capped min-max passes); scratch: nc bytes
 hipError_t launch_empty_map(const uint32_t* cell_start, int nx, int ny, int nz, uint8_t* out,
                             uint8_t* scratch, hipStream_t s,

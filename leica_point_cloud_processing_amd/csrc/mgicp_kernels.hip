@@ -31,7 +31,6 @@
 #ifndef MGICP_CORR_PHASES
 #define MGICP_CORR_PHASES 0  // 1: per-phase shader-clock totals of the wave 1-NN sweep (diagnostic builds only)
 #endif
-constexpr bool kSeedBox = true;  // seeded 1-NN queries search the cube of their seed's ball (box_search)
 constexpr int kRegListBatch = 8;  // register-list k-NN rows in guarded batches of this many points
 
 #include "mgicp_internal.hpp"
@@ -118,10 +117,9 @@ __device__ __forceinline__ int near_side(float q, float o, float h, int c) {
 // Visit grid rings (Chebyshev shells of cells) around q in increasing order until the
 // visitor proves that no unvisited point can enter its result.  A ring's rows of cells
 // are contiguous ranges of the sorted point array.
-// r_from > 0: rings below r_from were visited already (the staged block of knn_blk_kernel)
 template <class V>
 __device__ __forceinline__ void ring_search(const GridView& g, float qx, float qy, float qz,
-                                            V& vis, int r_from = 0) {
+                                            V& vis) {
   const int cx = qcell(qx, g.ox, g.inv_h), cy = qcell(qy, g.oy, g.inv_h),
             cz = qcell(qz, g.oz, g.inv_h);
   int rmin = max(max(dist_out(cx, g.nx), dist_out(cy, g.ny)), dist_out(cz, g.nz));
@@ -130,7 +128,7 @@ __device__ __forceinline__ void ring_search(const GridView& g, float qx, float q
     rmin = g.empty_dist[static_cast<size_t>(cx) +
                         static_cast<size_t>(g.nx) * (static_cast<size_t>(cy) + static_cast<size_t>(g.ny) * cz)];
   }
-  for (int r = max(rmin, r_from); r < (1 << 22); ++r) {
+  for (int r = rmin; r < (1 << 22); ++r) {
     if constexpr (V::kRingCap) {
       if (r > vis.ring_cap) {
         vis.gave_up = true;
@@ -209,82 +207,6 @@ __device__ __forceinline__ bool empty_reject(const GridView& g, float qx, float 
   if (L == INFINITY) return true;  // every cell lies in the empty box: the grid holds no point at all
   const float Ls = L * 0.99999f - g.slop;
   return Ls > 0.f && static_cast<double>(Ls) * static_cast<double>(Ls) >= thr;
-}
-
-// lower bound of the distance from q to a point box [lo, hi] (component-wise, each gap shrunk by
-// the rounding slop); an empty cell's sentinel box (lo = +INF, hi = -INF) gives +INF
-__device__ __forceinline__ float box_gap2(float qx, float qy, float qz, const float4& lo, const float4& hi,
-                                          float slop) {
-  const float gx = fmaxf(fmaxf(lo.x - qx, qx - hi.x) - slop, 0.f);
-  const float gy = fmaxf(fmaxf(lo.y - qy, qy - hi.y) - slop, 0.f);
-  const float gz = fmaxf(fmaxf(lo.z - qz, qz - hi.z) - slop, 0.f);
-  return gx * gx + gy * gy + gz * gz;
-}
-
-// Cells [xa, xb] of one grid row with their TIGHT point boxes (GridView::boxes): only the span
-// from the first to the last cell whose box can still hold a winner is scanned.  A query off a
-// surface (the 1-NN sweeps: 2-35 mm above the target) sees a whole slab of surface cells inside
-// its ball when cells are bounded by their grid boxes; by their point boxes only the cells next
-// to the foot of the query survive.  Exact: a skipped cell's every point lies beyond the bound.
-template <class V>
-__device__ __forceinline__ void visit_row_boxed(const GridView& g, size_t row, int xa, int xb, float w,
-                                                V& vis) {
-  uint32_t s = 0xffffffffu, e = 0u;
-  for (int x = xa; x <= xb; ++x) {
-    const float4 lo = g.boxes[2 * (row + x)], hi = g.boxes[2 * (row + x) + 1];
-    if (box_gap2(vis.qx, vis.qy, vis.qz, lo, hi, g.slop) <= w) {
-      s = min(s, __float_as_uint(lo.w));
-      e = max(e, __float_as_uint(hi.w));
-    }
-  }
-  if (s < e) vis.range(g, s, e);
-}
-
-// ring_search with per-cell point boxes (targets of the 1-NN sweeps): identical ring order,
-// termination and row pruning; inside a row the cell boxes decide which points are scanned
-template <class V>
-__device__ __forceinline__ void ring_search_boxed(const GridView& g, float qx, float qy, float qz,
-                                                  V& vis) {
-  const int cx = qcell(qx, g.ox, g.inv_h), cy = qcell(qy, g.oy, g.inv_h),
-            cz = qcell(qz, g.oz, g.inv_h);
-  int rmin = max(max(dist_out(cx, g.nx), dist_out(cy, g.ny)), dist_out(cz, g.nz));
-  if (rmin == 0 && g.empty_dist)
-    rmin = g.empty_dist[static_cast<size_t>(cx) +
-                        static_cast<size_t>(g.nx) * (static_cast<size_t>(cy) + static_cast<size_t>(g.ny) * cz)];
-  for (int r = rmin; r < (1 << 22); ++r) {
-    if (r > 0) {
-      const float L = fminf(fminf(axis_bound(qx, g.ox, g.h, cx, r - 1, g.nx),
-                                  axis_bound(qy, g.oy, g.h, cy, r - 1, g.ny)),
-                            axis_bound(qz, g.oz, g.h, cz, r - 1, g.nz));
-      if (L == INFINITY) return;
-      const float Ls = L * 0.99999f - g.slop;
-      if (vis.done(Ls)) return;
-    }
-    const int x0 = cx - r, x1 = cx + r, y0 = cy - r, y1 = cy + r, z0 = cz - r, z1 = cz + r;
-    const int xlo = max(x0, 0), xhi = min(x1, g.nx - 1);
-    const int ylo = max(y0, 0), yhi = min(y1, g.ny - 1);
-    const int zlo = max(z0, 0), zhi = min(z1, g.nz - 1);
-    for (int z = zlo; z <= zhi; ++z) {
-      const bool zf = (z == z0) || (z == z1);
-      const float gz = cell_gap(qz, g.oz, g.h, z, g.slop);
-      for (int y = ylo; y <= yhi; ++y) {
-        const float w = vis.prune2() * 1.00001f;
-        const float gy = cell_gap(qy, g.oy, g.h, y, g.slop);
-        const float gyz = gy * gy + gz * gz;
-        if (gyz > w) continue;
-        const size_t row = (static_cast<size_t>(z) * g.ny + y) * g.nx;
-        if (zf || y == y0 || y == y1) {
-          const float rx = sqrtf(w - gyz) + g.slop;
-          const int xa = max(xlo, qcell(qx - rx, g.ox, g.inv_h));
-          const int xb = min(xhi, qcell(qx + rx, g.ox, g.inv_h));
-          if (xa <= xb) visit_row_boxed(g, row, xa, xb, w, vis);
-        } else {
-          if (x0 >= 0) visit_row_boxed(g, row, x0, x0, w, vis);
-          if (x1 < g.nx) visit_row_boxed(g, row, x1, x1, vis.prune2() * 1.00001f, vis);
-        }
-      }
-    }
-  }
 }
 
 // exact k-NN visitor: register-resident sorted list of (d2, index) keys.  A runtime k < K is
@@ -459,16 +381,15 @@ __device__ __forceinline__ void lds_wave_sync() {
   __atomic_signal_fence(__ATOMIC_SEQ_CST);
 }
 
-// box_search over a wave's union box staged in LDS (r03, correspond_wave_kernel's small-ball
-// waves): the same rows, x-ranges, pruning and candidate keys as box_search -- so the same result --
-// with the cell bounds and the points read from the wave's LDS copy instead of dependent global
-// gathers.  Row s = (z - Z0) * nyb + (y - Y0) of the box holds its cells' starts for x = X0 .. X1 + 1
-// at lb[s * (nxb + 1) ..] (global sorted positions) and its points from lp[loff[s]] on; the
-// lane's ball (radius from its current best) lies inside the box by construction.
+// box_search over a wave's union box whose cell bounds are staged in LDS (r03, correspond_wave_kernel's
+// small-ball waves): the same rows, x-ranges, pruning and candidate keys as box_search -- so the same
+// result -- with the cell bounds read from the wave's LDS copy instead of dependent global gathers
+// (the candidates stay global gathers of the sorted points).  Row s = (z - Z0) * nyb + (y - Y0) of the
+// box holds its cells' starts for x = X0 .. X1 + 1 at lb[s * (nxb + 1) ..] (global sorted positions);
+// the lane's ball (radius from its current best) lies inside the box by construction.
 template <class V>
 __device__ __forceinline__ void box_search_lds(const GridView& g, float qx, float qy, float qz, V& vis, int Z0,
-                                               int Y0, int X0, int nyb, int nxb, const uint32_t* lb,
-                                               const uint32_t* loff, const float4* lp) {
+                                               int Y0, int X0, int nyb, int nxb, const uint32_t* lb) {
   const float R = sqrtf(vis.prune2() * 1.00001f) + g.slop;
   const int za = max(qcell(qz - R, g.oz, g.inv_h), 0), zb = min(qcell(qz + R, g.oz, g.inv_h), g.nz - 1);
   const int ya = max(qcell(qy - R, g.oy, g.inv_h), 0), yb = min(qcell(qy + R, g.oy, g.inv_h), g.ny - 1);
@@ -495,13 +416,8 @@ __device__ __forceinline__ void box_search_lds(const GridView& g, float qx, floa
       if (xa > xb) continue;
       const int sr = (z - Z0) * nyb + (y - Y0);
       const uint32_t* b = lb + sr * nb;
-      const uint32_t a0 = b[0], ja = b[xa - X0], jb = b[xb + 1 - X0];
-      if (lp) {
-        const float4* q = lp + loff[sr] + (ja - a0);
-        for (uint32_t j = ja; j < jb; ++j, ++q) vis.test(*q, j);
-      } else {
-        vis.range(g, ja, jb);  // bounds from LDS, candidates from the global sorted points
-      }
+      const uint32_t ja = b[xa - X0], jb = b[xb + 1 - X0];
+      vis.range(g, ja, jb);  // bounds from LDS, candidates from the global sorted points
     }
   }
 }
@@ -565,34 +481,16 @@ __global__ __launch_bounds__(256) void bbox_kernel(const float4* pts, size_t n, 
   if (threadIdx.x < 7) partial[blockIdx.x * 8 + threadIdx.x] = sm[threadIdx.x][0];
 }
 
-__global__ void cell_hist_kernel(const float4* pts, size_t n, float ox, float oy, float oz,
-                                 float inv_h, int nx, int ny, int nz, uint32_t* counts,
-                                 uint32_t* keys) {
+// linear cell index of every point: the keys of the grid's sort (the cell counts come from the sorted
+// keys, cell_end_kernel -- no histogram of atomics)
+__global__ void cell_keys_kernel(const float4* pts, size_t n, float ox, float oy, float oz,
+                                 float inv_h, int nx, int ny, int nz, uint32_t* keys) {
   const size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  const bool live = i < n;
-  uint32_t lin = 0xffffffffu;
-  if (live) {
-    const float4 p = pts[i];
-    const uint32_t cx = bcell(p.x, ox, inv_h, nx), cy = bcell(p.y, oy, inv_h, ny),
-                   cz = bcell(p.z, oz, inv_h, nz);
-    lin = cx + static_cast<uint32_t>(nx) * (cy + static_cast<uint32_t>(ny) * cz);
-    if (keys) keys[i] = lin;
-  }
-  if (!counts) return;  // r06: keys only (the grid's counts come from the sorted keys, cell_end_kernel)
-  // r03: scan-ordered clouds (a scanner's line order) put runs of consecutive points into one cell;
-  // the run's first lane adds the run length, one atomic per run instead of one per point.  The
-  // synthetic bench clouds are in random order (no runs): there the kernel stays bound by the
-  // memory-side atomics (~260 us per 5M points, profiles/r03/prep)
-  const int lane = threadIdx.x & 63;
-  const uint32_t prev = __shfl_up(lin, 1, 64);
-  const bool head = live && (lane == 0 || prev != lin);
-  const unsigned long long hm = __builtin_amdgcn_ballot_w64(head);
-  const unsigned long long lm = __builtin_amdgcn_ballot_w64(live);
-  if (head) {
-    const unsigned long long above = hm & ~((2ull << lane) - 1ull);  // heads after this lane
-    const int next = above ? __builtin_ctzll(above) : 64 - __builtin_clzll(lm);  // run end (exclusive)
-    atomicAdd(&counts[lin], static_cast<uint32_t>(next - lane));
-  }
+  if (i >= n) return;
+  const float4 p = pts[i];
+  const uint32_t cx = bcell(p.x, ox, inv_h, nx), cy = bcell(p.y, oy, inv_h, ny),
+                 cz = bcell(p.z, oz, inv_h, nz);
+  keys[i] = cx + static_cast<uint32_t>(nx) * (cy + static_cast<uint32_t>(ny) * cz);
 }
 
 // r06: the grid's sizing sketch.  build_grid aims at ~10 points per non-empty cell; r01-r05 found the cell
@@ -779,23 +677,6 @@ __global__ __launch_bounds__(256) void empty_pass_kernel(const uint8_t* __restri
   }
 }
 
-// per-cell point boxes: boxes[2c] = (min x, min y, min z, bits(start)), boxes[2c + 1] =
-// (max x, max y, max z, bits(end)); an empty cell gets the sentinel (+INF / -INF) box
-__global__ void cell_box_kernel(const float4* __restrict__ pts, const uint32_t* __restrict__ cs, size_t nc,
-                                float4* __restrict__ boxes) {
-  const size_t c = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (c >= nc) return;
-  const uint32_t a = cs[c], b = cs[c + 1];
-  float lx = INFINITY, ly = INFINITY, lz = INFINITY, hx = -INFINITY, hy = -INFINITY, hz = -INFINITY;
-  for (uint32_t j = a; j < b; ++j) {
-    const float4 p = pts[j];
-    lx = fminf(lx, p.x); ly = fminf(ly, p.y); lz = fminf(lz, p.z);
-    hx = fmaxf(hx, p.x); hy = fmaxf(hy, p.y); hz = fmaxf(hz, p.z);
-  }
-  boxes[2 * c] = make_float4(lx, ly, lz, __uint_as_float(a));
-  boxes[2 * c + 1] = make_float4(hx, hy, hz, __uint_as_float(b));
-}
-
 __global__ void iota_kernel(uint32_t* v, size_t n) {
   const size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
   if (i < n) v[i] = static_cast<uint32_t>(i);
@@ -860,7 +741,7 @@ __device__ __forceinline__ double sel3(int i, double a, double b, double c) {
 // final k-NN set (ties at the final k-th included) -- no second search.
 #define MGICP_KNN_LOG_BATCH 8  // log entries read per batch (compaction, moments): loads in flight together
 constexpr int kLogBatch = MGICP_KNN_LOG_BATCH;
-#define MGICP_KNN_RANGE_BATCH 8  // candidates per guarded batch of the logged k-NN rows (0: 4-wide + tail)
+constexpr int kRangeBatch = 8;  // candidates per guarded batch of the logged k-NN rows
 
 template <int K>
 struct KthVisitor {
@@ -919,29 +800,16 @@ struct KthVisitor {
     }
   }
   __device__ __forceinline__ void range(const GridView& g, uint32_t a, uint32_t b) {
-#if MGICP_KNN_RANGE_BATCH
     // guarded batches: every load of a batch in flight at once, a row's tail included (the
     // clamped duplicate loads hit the same lines; their tests are skipped)
-    for (uint32_t j0 = a; j0 < b; j0 += MGICP_KNN_RANGE_BATCH) {
-      float4 pb[MGICP_KNN_RANGE_BATCH];
+    for (uint32_t j0 = a; j0 < b; j0 += kRangeBatch) {
+      float4 pb[kRangeBatch];
 #pragma unroll
-      for (int u = 0; u < MGICP_KNN_RANGE_BATCH; ++u) pb[u] = g.pts[min(j0 + u, b - 1)];
+      for (int u = 0; u < kRangeBatch; ++u) pb[u] = g.pts[min(j0 + u, b - 1)];
 #pragma unroll
-      for (int u = 0; u < MGICP_KNN_RANGE_BATCH; ++u)
+      for (int u = 0; u < kRangeBatch; ++u)
         if (j0 + u < b) test(dist2(qx, qy, qz, pb[u]), pb[u].w, j0 + u);
     }
-#else
-    const float4* q = g.pts + a;
-    uint32_t j = a;
-    for (; j + 4 <= b; j += 4, q += 4) {
-      const float4 p0 = q[0], p1 = q[1], p2 = q[2], p3 = q[3];
-      test(dist2(qx, qy, qz, p0), p0.w, j);
-      test(dist2(qx, qy, qz, p1), p1.w, j + 1);
-      test(dist2(qx, qy, qz, p2), p2.w, j + 2);
-      test(dist2(qx, qy, qz, p3), p3.w, j + 3);
-    }
-    for (; j < b; ++j, ++q) test(dist2(qx, qy, qz, *q), q->w, j);
-#endif
   }
 };
 
@@ -1426,7 +1294,7 @@ __device__ __forceinline__ void seed_query(const GridView& tg, int seeded, uint3
 }
 
 // ---- wave-uniform 1-NN sweep (r03) ----------------------------------------------------------
-// The per-lane search (correspond_kernel) issues one 16-byte gather per candidate and lane; its 64
+// The per-lane search (box_search / ring_search) issues one 16-byte gather per candidate and lane; its 64
 // lanes touch ~18 cache lines per load, and the texture addresser was busy 87-88 % of every sweep
 // (TA_TA_BUSY, profiles/r03/corrdiag): the sweeps were bound by vector-memory ADDRESS throughput,
 // not by bytes or arithmetic.  Here the 64 Morton-ordered queries of a wave scan the rows of their
@@ -1443,15 +1311,6 @@ __device__ __forceinline__ void seed_query(const GridView& tg, int seeded, uint3
 // per-lane search from their best.
 typedef float f2v __attribute__((ext_vector_type(2)));
 typedef float f4v __attribute__((ext_vector_type(4)));
-
-// r03: lanes the union scan does not settle are handed to correspond_finish_kernel through a work
-// list instead of finishing in place -- in place, a wave waited for its slowest straggler with the
-// other lanes idle (62 % of the first sweep's waves had one; 66 % of its wave time)
-struct NnWork {
-  uint32_t q;     // shard-relative source position
-  uint32_t pos;   // the visitor's best so far (sorted target position)
-  unsigned long long best;  // its (d2 bits << 32 | index) key, ~0 = none
-};
 
 __device__ __forceinline__ int wave_min_i(int v) {
 #pragma unroll
@@ -1483,19 +1342,16 @@ __device__ __forceinline__ void pair_d2(float qx, float qy, float qz, const f4v&
 
 constexpr int kStagePairs = 64;     // pairs staged per wave and chunk (128 candidates, 2 KiB of LDS)
 constexpr int kCorrRowSlots = 256;  // union-box rows whose cell bounds a wave keeps in registers (4 per lane)
-constexpr int kLdsRows = 64;        // small-ball LDS path: rows of the union box (one per lane in the scan)
+constexpr int kLdsRows = 64;        // small-ball LDS path: rows of the union box
 constexpr int kLdsBounds = 256;     // cell starts of the box kept in LDS (rows x (x cells + 1))
-constexpr int kLdsMeta = (kLdsBounds + kLdsRows) / 4;  // float4 slots of the bounds + row offsets
-constexpr int kLdsMaxPts = 512;     // largest lds_cap the kernel is built for (points per wave)
+constexpr int kLdsMeta = kLdsBounds / 4;  // float4 slots of the bounds, per wave
 
 __global__ __launch_bounds__(256, MGICP_CORR_WAVES) void correspond_wave_kernel(
     GridView tg, const float4* __restrict__ src, size_t p0, size_t p1, Xf34 T, double thr, int seeded,
     uint32_t* __restrict__ nn_pos, uint32_t* __restrict__ flags, const uint32_t* __restrict__ qperm, float rcap2,
-    int max_rows, int max_xcells, float union_min_r, NnWork* __restrict__ work, unsigned int* __restrict__ work_n,
-    int split_max, int lds_cap) {
+    int max_rows, int max_xcells, float union_min_r) {
   __shared__ f4v stage[4][2 * kStagePairs];
-  // small-ball waves: the union box's cell bounds, row offsets and points (dynamic LDS, lds_cap
-  // points per wave; 0 = off)
+  // small-ball waves: the union box's cell bounds (dynamic LDS, kLdsMeta float4 per wave)
   extern __shared__ float4 s_lds[];
   const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const size_t t = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
@@ -1658,15 +1514,13 @@ __global__ __launch_bounds__(256, MGICP_CORR_WAVES) void correspond_wave_kernel(
     }
 #endif
   }
-  // ---- small-ball waves (union scan not worth it): stage the union box once per wave in LDS, then
-  // every included lane runs the exact box search from its seed bound on the LDS copy
-  if (!box_ok && lds_cap != 0 && Z0 <= Z1 && Y0 <= Y1 && X0 <= X1) {
+  // ---- small-ball waves (union scan not worth it): stage the union box's cell bounds once per wave in
+  // LDS, then every included lane runs the exact box search from its seed bound on them (the candidates
+  // stay global gathers of the sorted points)
+  if (!box_ok && Z0 <= Z1 && Y0 <= Y1 && X0 <= X1) {
     const int nyb = Y1 - Y0 + 1, nxb = X1 - X0 + 1, nrows = (Z1 - Z0 + 1) * nyb, nb = nxb + 1;
     if (nrows <= kLdsRows && nrows * nb <= kLdsBounds) {
-      const int cap = max(lds_cap, 0);  // lds_cap < 0: cell bounds only, candidates stay global gathers
-      uint32_t* lb = reinterpret_cast<uint32_t*>(s_lds + static_cast<size_t>(wid) * (cap + kLdsMeta));
-      uint32_t* loff = lb + kLdsBounds;
-      float4* lp = s_lds + static_cast<size_t>(wid) * (cap + kLdsMeta) + kLdsMeta;
+      uint32_t* lb = reinterpret_cast<uint32_t*>(s_lds + static_cast<size_t>(wid) * kLdsMeta);
       // cell starts of every row of the box for x = X0 .. X1 + 1 (independent loads)
       uint32_t cb[kLdsBounds / 64];
 #pragma unroll
@@ -1680,48 +1534,9 @@ __global__ __launch_bounds__(256, MGICP_CORR_WAVES) void correspond_wave_kernel(
       for (int k = 0; k < kLdsBounds / 64; ++k)
         if (lane + 64 * k < nrows * nb) lb[lane + 64 * k] = cb[k];
       lds_wave_sync();
-      // row s (lane s) holds lb[s][nxb] - lb[s][0] points: exclusive scan over the rows
-      const uint32_t cnt = lane < nrows ? lb[lane * nb + nxb] - lb[lane * nb] : 0u;
-      uint32_t inc = cnt;
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t u = __shfl_up(inc, off, 64);
-        if (lane >= off) inc += u;
-      }
-      const uint32_t npts = __builtin_amdgcn_readlane(inc, 63);
-      if (lane < nrows) loff[lane] = inc - cnt;
-      lds_wave_sync();
-      if (lds_cap < 0) {
-        if (incl0) box_search_lds(tg, qx, qy, qz, vis, Z0, Y0, X0, nyb, nxb, lb, loff, static_cast<const float4*>(nullptr));
-        incl = incl0;
-        tie = false;
-      } else if (npts <= static_cast<uint32_t>(cap)) {
-        // the points, in box order: slot t belongs to the last row whose offset is <= t
-        for (uint32_t k0 = 0; k0 < npts; k0 += 256) {  // 4 loads per lane in flight per round
-        float4 v[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const uint32_t tt = k0 + static_cast<uint32_t>(lane + 64 * k);
-          uint32_t gp = 0;
-          if (tt < npts) {
-            int lo = 0, hi = nrows - 1;
-            while (lo < hi) {
-              const int mid = (lo + hi + 1) >> 1;
-              if (loff[mid] <= tt) lo = mid; else hi = mid - 1;
-            }
-            gp = lb[lo * nb] + (tt - loff[lo]);
-          }
-          v[k] = tg.pts[gp];
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-          if (k0 + static_cast<uint32_t>(lane + 64 * k) < npts) lp[k0 + lane + 64 * k] = v[k];
-        }
-        lds_wave_sync();
-        if (incl0) box_search_lds(tg, qx, qy, qz, vis, Z0, Y0, X0, nyb, nxb, lb, loff, lp);
-        incl = incl0;  // settled exactly (keys decide ties): only lanes without a seed ball remain
-        tie = false;
-      }
+      if (incl0) box_search_lds(tg, qx, qy, qz, vis, Z0, Y0, X0, nyb, nxb, lb);
+      incl = incl0;  // settled exactly (keys decide ties): only lanes without a seed ball remain
+      tie = false;
     }
   }
   MGICP_PH(3);
@@ -1739,27 +1554,11 @@ __global__ __launch_bounds__(256, MGICP_CORR_WAVES) void correspond_wave_kernel(
     }
   }
 #endif
-  const unsigned long long fm = __builtin_amdgcn_ballot_w64(fin);
-  if (work && __builtin_popcountll(fm) <= split_max) {
-    // hand the stragglers on: one atomic per wave, slots in lane order
-    const unsigned long long m = fm;
-    if (m) {
-      unsigned int base = 0;
-      if (lane == 0) base = atomicAdd(work_n, static_cast<unsigned int>(__builtin_popcountll(m)));
-      base = __builtin_amdgcn_readfirstlane(base);
-      const unsigned int off = __builtin_amdgcn_mbcnt_hi(static_cast<unsigned int>(m >> 32),
-                                                         __builtin_amdgcn_mbcnt_lo(static_cast<unsigned int>(m), 0u));
-      if (fin) work[base + off] = NnWork{static_cast<uint32_t>(p - p0), vis.pos, vis.best};
-    }
-    MGICP_PH(4);
-    if (!live || fin) return;
-  } else {
-    if (fin) {
-      if (vis.best != ~0ull) box_search(tg, qx, qy, qz, vis);
-      else ring_search(tg, qx, qy, qz, vis);
-    }
-    MGICP_PH(4);
+  if (fin) {
+    if (vis.best != ~0ull) box_search(tg, qx, qy, qz, vis);
+    else ring_search(tg, qx, qy, qz, vis);
   }
+  MGICP_PH(4);
   if (!live) return;
   const bool ok = vis.best != ~0ull &&
                   static_cast<double>(__uint_as_float(static_cast<uint32_t>(vis.best >> 32))) < thr;
@@ -1776,31 +1575,6 @@ __global__ __launch_bounds__(256, MGICP_CORR_WAVES) void correspond_wave_kernel(
 #endif
 }
 
-// The stragglers of correspond_wave_kernel: the per-lane exact search from the visitor state the
-// union scan left (a real candidate and its key, or none), 64 of them per wave.  Grid-stride over
-// the device-side count.
-__global__ __launch_bounds__(256, MGICP_CORR_WAVES) void correspond_finish_kernel(
-    GridView tg, const float4* __restrict__ src, size_t p0, Xf34 T, double thr, const NnWork* __restrict__ work,
-    const unsigned int* __restrict__ work_n, uint32_t* __restrict__ nn_pos, uint32_t* __restrict__ flags) {
-  const unsigned int n = *work_n;
-  for (unsigned int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    const NnWork w = work[i];
-    const float4 s = src[p0 + w.q];
-    float qx, qy, qz;
-    xform(T, s.x, s.y, s.z, qx, qy, qz);
-    NnVisitor vis;
-    vis.init(qx, qy, qz, thr);
-    vis.best = w.best;
-    vis.pos = w.pos;
-    if (vis.best != ~0ull) box_search(tg, qx, qy, qz, vis);
-    else ring_search(tg, qx, qy, qz, vis);
-    const bool ok = vis.best != ~0ull &&
-                    static_cast<double>(__uint_as_float(static_cast<uint32_t>(vis.best >> 32))) < thr;
-    nn_pos[w.q] = ok ? vis.pos : 0xffffffffu;
-    flags[w.q] = ok ? 1u : 0u;
-  }
-}
-
 // pair-interleaved copy of the sorted points (GridView::pairs): pair i = {x_2i, x_2i+1, y.., y..,
 // z.., z.., bits(w_2i), bits(w_2i+1)}; positions past n are far sentinels (d2 = +inf, w = ~0)
 __global__ void pairs_kernel(const float4* __restrict__ pts, size_t n, size_t npairs, float4* __restrict__ out) {
@@ -1811,68 +1585,6 @@ __global__ void pairs_kernel(const float4* __restrict__ pts, size_t n, size_t np
   const float4 a = 2 * i < n ? pts[2 * i] : s, b = 2 * i + 1 < n ? pts[2 * i + 1] : s;
   out[2 * i] = make_float4(a.x, b.x, a.y, b.y);
   out[2 * i + 1] = make_float4(a.z, b.z, a.w, b.w);
-}
-
-__global__ __launch_bounds__(256, MGICP_CORR_WAVES) void correspond_kernel(GridView tg, const float4* __restrict__ src,
-                                                         size_t p0, size_t p1, Xf34 T, double thr,
-                                                         int seeded, uint32_t* __restrict__ nn_pos,
-                                                         uint32_t* __restrict__ flags,
-                                                         const uint32_t* __restrict__ qperm) {
-  const size_t t = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (t >= p1 - p0) return;
-  const size_t p = p0 + (qperm ? qperm[t] : t);
-  const float4 s = src[p];
-  float qx, qy, qz;
-  xform(T, s.x, s.y, s.z, qx, qy, qz);
-  NnVisitor vis;
-  vis.init(qx, qy, qz, thr);
-  if (seeded) {
-    // seed with last iteration's match: a real candidate, so the exact search only tightens it,
-    // and the ball-cell pruning starts from a near-final radius
-    const uint32_t pp = nn_pos[p - p0];
-    if (pp != 0xffffffffu) vis.range(tg, pp, pp + 1);
-  }
-  if (tg.seed) {  // seeded sweeps also test the seed map's candidate (the nearer one wins)
-    if (!seeded) {
-      // the first sweep: the seeds of the query's cell and its 6 face neighbours, the nearest wins
-      const int cx = qcell(qx, tg.ox, tg.inv_h), cy = qcell(qy, tg.oy, tg.inv_h), cz = qcell(qz, tg.oz, tg.inv_h);
-      const int dd[7][3] = {{0, 0, 0}, {-1, 0, 0}, {1, 0, 0}, {0, -1, 0}, {0, 1, 0}, {0, 0, -1}, {0, 0, 1}};
-#pragma unroll
-      for (int k = 0; k < 7; ++k) {
-        const int x = cx + dd[k][0], y = cy + dd[k][1], z = cz + dd[k][2];
-        if (x >= 0 && x < tg.nx && y >= 0 && y < tg.ny && z >= 0 && z < tg.nz) {
-          const uint32_t pp = tg.seed[static_cast<size_t>(x) +
-                                      static_cast<size_t>(tg.nx) * (static_cast<size_t>(y) + static_cast<size_t>(tg.ny) * z)];
-          if (pp != 0xffffffffu) vis.range(tg, pp, pp + 1);
-        }
-      }
-    } else
-    {
-      // a point of a Chebyshev-nearest non-empty cell (seed map): the first sweep's seed, and in
-      // later sweeps a second candidate beside the last match (queries move by up to centimetres
-      // after the first BFGS run) -- any real candidate keeps the search exact and lets box_search
-      // prune from its first row
-      const int cx = qcell(qx, tg.ox, tg.inv_h), cy = qcell(qy, tg.oy, tg.inv_h), cz = qcell(qz, tg.oz, tg.inv_h);
-      if (cx >= 0 && cx < tg.nx && cy >= 0 && cy < tg.ny && cz >= 0 && cz < tg.nz) {
-        const uint32_t pp = tg.seed[static_cast<size_t>(cx) +
-                                    static_cast<size_t>(tg.nx) * (static_cast<size_t>(cy) + static_cast<size_t>(tg.ny) * cz)];
-        if (pp != 0xffffffffu) vis.range(tg, pp, pp + 1);
-      }
-    }
-  }
-  if (tg.boxes) ring_search_boxed(tg, qx, qy, qz, vis);
-  else if (kSeedBox && vis.best != ~0ull) box_search(tg, qx, qy, qz, vis);
-  else ring_search(tg, qx, qy, qz, vis);
-  const bool ok = vis.best != ~0ull &&
-                  static_cast<double>(__uint_as_float(static_cast<uint32_t>(vis.best >> 32))) < thr;
-  nn_pos[p - p0] = ok ? vis.pos : 0xffffffffu;
-  flags[p - p0] = ok ? 1u : 0u;
-#if MGICP_CORR_STATS
-  atomicAdd(&g_corr_stats[0], 1ull);
-  atomicAdd(&g_corr_stats[ok ? 1 : 2], 1ull);
-  atomicAdd(&g_corr_stats[ok ? 3 : 4], static_cast<unsigned long long>(vis.ntest));
-  atomicAdd(&g_corr_stats[ok ? 5 : 6], static_cast<unsigned long long>(vis.nrange));
-#endif
 }
 
 // ---- 1-NN cell lists (r04): DESIGN.md "1-NN cell lists" ---------------------------------------------
@@ -2526,7 +2238,7 @@ __global__ __launch_bounds__(64 * kVlWaves) void vl_build_large_kernel(GridView 
   }
 }
 
-// the sweep's queries without a list: the exact per-lane search, seeded as in correspond_kernel
+// the sweep's queries without a list: the exact per-lane search, seeded as in correspond_wave_kernel
 __global__ __launch_bounds__(256) void vl_fallback_kernel(GridView tg, VListView v, const float4* __restrict__ src,
                                                           size_t p0, Xf34 T, double thr, int seeded,
                                                           uint32_t* __restrict__ nn_pos, uint32_t* __restrict__ flags) {
@@ -3362,20 +3074,9 @@ __device__ __forceinline__ void fdf_soa_body(CorrSoA c, const uint32_t* __restri
       load_group(c, i, g);
       fdf_group(A, g, acc);
     }
-    if (reverse & 2) {  // timing diagnostics only (MGICP_FDF_DIAG): stream, no reduction
-      if (acc[0] == 12345.0) partial[j] = acc[1];
-      continue;
-    }
-    if (reverse & 4) {  // timing diagnostics only: chunk partials, no tickets
-#pragma unroll
-      for (int v = 0; v < 13; ++v) acc[v] = wave_sum(acc[v]);
-      if (lane == 0)
-        for (int v = 0; v < 13; ++v) partial[static_cast<size_t>(j) * kRedVals + v] = acc[v];
-      continue;
-    }
     chunk_store(j, acc, ccnt, partial, lane);
   }
-  if (w0 >= nch || (reverse & 6)) return;
+  if (w0 >= nch) return;
   wave_tickets(w0, nw, nch, reverse, tickets, partial, spart, out, done_flag, seq, lane, host_rows, false, rstamp);
 }
 
@@ -3396,20 +3097,10 @@ __device__ __forceinline__ void fdf_soa_body(CorrSoA c, const uint32_t* __restri
 // because one wave per SIMD keeps few loads in flight; software-pipelining the streamed groups in
 // registers (2-3 resident groups, spills) or through an LDS-DMA ring (3 resident groups) measured
 // 67-77 us per pass against ~65 us for this form and ~66-70 us for launched passes.
-// Two shapes (env MGICP_SRV_WAVES): 4 waves per CU (1 per SIMD, 512 VGPR+AGPR) holding a whole chunk
-// in registers + 2 groups in LDS (31 % of C4's bytes on chip), or 8 waves per CU (2 per SIMD, 256
-// registers) holding 1 group in registers + 1 in LDS each (21 %) with two waves per SIMD to
-// overlap the streamed loads.
-template <int kWaves>
-struct SrvShape;
-template <>
-struct SrvShape<4> {
-  static constexpr int kReg = 4, kLds = 2;  // kReg = 4: the LDS groups are chunk 1's first kLds
-};
-template <>
-struct SrvShape<8> {
-  static constexpr int kReg = 1, kLds = 1;  // kReg < 4: the LDS groups follow in chunk 0
-};
+// The one shape: 4 waves per CU (1 per SIMD, 512 VGPR+AGPR) holding a whole chunk in registers + 2
+// groups in LDS (31 % of C4's bytes on chip).  An 8-waves-per-CU shape (2 per SIMD, 256 registers, 1
+// group in registers + 1 in LDS each: 21 %) measured 57.7-58.0 vs 50.2-50.3 us per pass
+// (profiles/r03/srv8) and is not built.
 
 // kBench: the timing instantiation (bench_passes > 0) -- a symbol of its own, so a rocprofv3 kernel
 // trace separates it from the servers of the aligns (its duration / bench_passes = one pass)
@@ -3423,16 +3114,15 @@ __global__ __launch_bounds__(64 * kWaves, 1) void fdf_server_kernel(
     PassCmd* mail, unsigned long long timeout, unsigned long long* ptimes, int bench_passes, Xf34 Abench,
     unsigned long long* host_rows, size_t rows_stride, int pollers, int stall_pass,
     unsigned long long* __restrict__ tpart, PeerRows peers) {
-  constexpr int kR = SrvShape<kWaves>::kReg, kL = SrvShape<kWaves>::kLds;
-  static_assert(kR <= 4 && (kR == 4 || kR + kL <= 4), "resident groups: chunk 0, then chunk 1 only after a full chunk 0");
+  static_assert(kWaves == 4, "the server's one shape: a 4-wave block per CU, one wave per SIMD");
+  constexpr int kR = 4, kL = 2;  // resident groups: chunk w0 whole in registers, chunk w1's first kL in LDS
   __shared__ float4 lf[kWaves][kL][6][64];
   __shared__ double2 ld[kWaves][kL][12][64];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int nw = gridDim.x * kWaves;
   const int w0 = __builtin_amdgcn_readfirstlane(static_cast<int>(blockIdx.x * kWaves + wid));
-  // resident data: groups [0, kR) of chunk w0 in registers; kLds groups in LDS -- chunk w1's first
-  // ones when chunk w0 is whole in registers, else chunk w0's next ones (each lane reads back only
-  // its own slots, so no barrier is needed)
+  // resident data: the kR groups of chunk w0 in registers; kL groups in LDS -- chunk w1's first ones
+  // (each lane reads back only its own slots, so no barrier is needed)
   const int w1 = w0 + nw;
   CorrGroup R[kR];
   uint32_t rb = 0, re = 0, lb = 0, le = 0;
@@ -3440,12 +3130,9 @@ __global__ __launch_bounds__(64 * kWaves, 1) void fdf_server_kernel(
     rb = chunk_g0(w0);
     re = chunk_g1(ccnt, w0);
   }
-  if (kR == 4 && w1 < nch) {
+  if (w1 < nch) {
     lb = chunk_g0(w1);
     le = chunk_g1(ccnt, w1);
-  } else if (kR < 4) {
-    lb = rb + 64 * kR;
-    le = re;
   }
 #pragma unroll
   for (int k = 0; k < kR; ++k)
@@ -3525,31 +3212,17 @@ __global__ __launch_bounds__(64 * kWaves, 1) void fdf_server_kernel(
 #pragma unroll
       for (int k = 0; k < kR; ++k)
         if (rb + lane + 64 * k < re) fdf_group(A, R[k], acc);
-      if (kR < 4) {
-#pragma unroll
-        for (int k = 0; k < kL; ++k)
-          if (lb + lane + 64 * k < le) lds_group(k, A, acc);
-        for (uint32_t i = rb + lane + 64 * (kR + kL); i < re; i += 64) {
-          CorrGroup g;
-          load_group(c, i, g);
-          fdf_group(A, g, acc);
-        }
-      }
       store(w0, acc);
     }
     if (w1 < nch) {
       double acc[kRedVals];
 #pragma unroll
       for (int v = 0; v < kRedVals; ++v) acc[v] = 0.0;
-      uint32_t i0 = chunk_g0(w1) + lane;
-      if (kR == 4) {
 #pragma unroll
-        for (int k = 0; k < kL; ++k)
-          if (lb + lane + 64 * k < le) lds_group(k, A, acc);
-        i0 = lb + lane + 64 * kL;
-      }
+      for (int k = 0; k < kL; ++k)
+        if (lb + lane + 64 * k < le) lds_group(k, A, acc);
       const uint32_t g1 = chunk_g1(ccnt, w1);
-      for (uint32_t i = i0; i < g1; i += 64) {
+      for (uint32_t i = lb + lane + 64 * kL; i < g1; i += 64) {
         CorrGroup g;
         load_group(c, i, g);
         fdf_group(A, g, acc);
@@ -3730,8 +3403,7 @@ __global__ __launch_bounds__(256) void fitness_kernel(GridView tg, const float4*
     xform(T, s.x, s.y, s.z, qx, qy, qz);
     NnVisitor vis;
     vis.init(qx, qy, qz, INFINITY);
-    if (tg.boxes) ring_search_boxed(tg, qx, qy, qz, vis);
-    else ring_search(tg, qx, qy, qz, vis);
+    ring_search(tg, qx, qy, qz, vis);
     if (vis.best != ~0ull) {
       const float d2 = __uint_as_float(static_cast<uint32_t>(vis.best >> 32));
       if (static_cast<double>(d2) <= max_range) {
@@ -3951,11 +3623,10 @@ hipError_t launch_bbox(const float4* pts, size_t n, float* partial, int nb, hipS
   return hipGetLastError();
 }
 
-hipError_t launch_cell_hist(const float4* pts, size_t n, float ox, float oy, float oz,
-                            float inv_h, int nx, int ny, int nz, uint32_t* counts,
-                            uint32_t* keys, hipStream_t s) {
+hipError_t launch_cell_keys(const float4* pts, size_t n, float ox, float oy, float oz,
+                            float inv_h, int nx, int ny, int nz, uint32_t* keys, hipStream_t s) {
   if (!n) return hipSuccess;
-  cell_hist_kernel<<<nblk(n), 256, 0, s>>>(pts, n, ox, oy, oz, inv_h, nx, ny, nz, counts, keys);
+  cell_keys_kernel<<<nblk(n), 256, 0, s>>>(pts, n, ox, oy, oz, inv_h, nx, ny, nz, keys);
   return hipGetLastError();
 }
 
@@ -4017,13 +3688,6 @@ hipError_t launch_empty_map(const uint32_t* cell_start, int nx, int ny, int nz, 
   pass(scratch, out, nx, 1, s2, seed);
   pass(out, scratch, ny, static_cast<size_t>(nx), seed, s2);
   pass(scratch, out, nz, static_cast<size_t>(nx) * ny, s2, seed);
-  return hipGetLastError();
-}
-
-hipError_t launch_cell_boxes(const float4* pts, const uint32_t* cell_start, size_t nc, float4* boxes,
-                             hipStream_t s) {
-  if (!nc) return hipSuccess;
-  cell_box_kernel<<<nblk(nc), 256, 0, s>>>(pts, cell_start, nc, boxes);
   return hipGetLastError();
 }
 
@@ -4207,39 +3871,25 @@ hipError_t launch_vl_stats(const VListView& vl, size_t ncells, unsigned long lon
   return hipGetLastError();
 }
 
-hipError_t launch_correspond(const GridView& tgt, const float4* src, size_t p0, size_t p1, Xf34 T,
-                             double thr, int seeded, uint32_t* nn_pos, uint32_t* flags,
-                             const uint32_t* qperm, hipStream_t s) {
-  if (p1 <= p0) return hipSuccess;
-  correspond_kernel<<<nblk(p1 - p0), 256, 0, s>>>(tgt, src, p0, p1, T, thr, seeded, nn_pos, flags, qperm);
-  return hipGetLastError();
-}
+// The wave sweep's limits, in cells of the target grid.  r03 A/B (profiles/r03/corrsweep): union boxes
+// of <= 96 rows and 16 cells along x, for waves whose mean seed bound is >= 1.25 cells (the first sweep
+// mostly): 2455 -> 2300 us per C4 align's sweeps
+constexpr float kCorrRcap = 5.f;          // lanes with a larger seed bound search alone
+constexpr int kCorrMaxRows = 96;          // union boxes with more rows / x cells: per-lane search
+constexpr int kCorrMaxXCells = 16;
+constexpr float kCorrUnionMinR = 1.25f;   // waves whose mean seed bound is smaller search per lane
 
 hipError_t launch_correspond_wave(const GridView& tgt, const float4* src, size_t p0, size_t p1, Xf34 T,
                                   double thr, int seeded, uint32_t* nn_pos, uint32_t* flags, const uint32_t* qperm,
-                                  float rcap2, int max_rows, int max_xcells, float union_min_r, void* work,
-                                  unsigned int* work_n, int split_max, int lds_cap, hipStream_t s) {
+                                  hipStream_t s) {
   if (p1 <= p0) return hipSuccess;
-  if (!tgt.pairs || (work && !work_n)) return hipErrorInvalidValue;
-  NnWork* w = static_cast<NnWork*>(work);
-  if (w) {
-    hipError_t e = hipMemsetAsync(work_n, 0, sizeof(unsigned int), s);
-    if (e != hipSuccess) return e;
-  }
-  if (lds_cap > 0) lds_cap = std::min(lds_cap, kLdsMaxPts) & ~63;
-  const size_t shm = lds_cap ? 4 * static_cast<size_t>(std::max(lds_cap, 0) + kLdsMeta) * sizeof(float4) : 0;
+  if (!tgt.pairs) return hipErrorInvalidValue;
+  const float rc = kCorrRcap * tgt.h;
+  const size_t shm = 4 * kLdsMeta * sizeof(float4);  // the small-ball waves' cell bounds, per wave
   correspond_wave_kernel<<<nblk(p1 - p0), 256, shm, s>>>(tgt, src, p0, p1, T, thr, seeded, nn_pos, flags, qperm,
-                                                         rcap2, max_rows, max_xcells, union_min_r, w, work_n,
-                                                         split_max, lds_cap);
-  if (w) {
-    // grid-stride over the stragglers: 8 blocks of 4 waves per CU (the count is known on the device only)
-    const unsigned int nb = static_cast<unsigned int>(std::min<size_t>(nblk(p1 - p0), 2048));
-    correspond_finish_kernel<<<nb, 256, 0, s>>>(tgt, src, p0, T, thr, w, work_n, nn_pos, flags);
-  }
+                                                         rc * rc, kCorrMaxRows, kCorrMaxXCells, kCorrUnionMinR);
   return hipGetLastError();
 }
-
-size_t nn_work_bytes(size_t n) { return n * sizeof(NnWork); }
 
 size_t pair_count(size_t n) { return (n + 1) / 2 + kStagePairs + 2; }
 
@@ -4293,13 +3943,15 @@ hipError_t launch_fdf_soa_gated(const CorrSoA& c, const uint32_t* ccnt, size_t n
   return hipGetLastError();
 }
 
-int fdf_server_blocks(size_t ns, int cus, int waves) {
-  // one block of `waves` waves per CU, fewer when the shard has fewer chunks; 0 when a wave would
+constexpr int kSrvWaves = 4;  // the server's block: 4 waves per CU, one per SIMD
+
+int fdf_server_blocks(size_t ns, int cus) {
+  // one block of kSrvWaves waves per CU, fewer when the shard has fewer chunks; 0 when a wave would
   // hold more than 64 chunks (its lanes draw the tickets of all its chunks at once)
   const int nch = chunk_count(ns);
-  if (nch == 0 || cus <= 0 || (waves != 4 && waves != 8)) return 0;
-  const int nb = std::min(cus, (nch + waves - 1) / waves);
-  if (nch > 64 * waves * nb) return 0;
+  if (nch == 0 || cus <= 0) return 0;
+  const int nb = std::min(cus, (nch + kSrvWaves - 1) / kSrvWaves);
+  if (nch > 64 * kSrvWaves * nb) return 0;
   return nb;
 }
 
@@ -4307,15 +3959,13 @@ hipError_t launch_fdf_server(const CorrSoA& c, const uint32_t* ccnt, size_t ns, 
                              double* spart, unsigned int* tickets, double* out, unsigned long long* done_flag,
                              unsigned long long seq0, const PassCmd* cmd, PassCmd* mail,
                              unsigned long long timeout_ticks, unsigned long long* ptimes, int bench_passes,
-                             Xf34 A, unsigned long long* host_rows, size_t rows_stride, int nb, int waves,
+                             Xf34 A, unsigned long long* host_rows, size_t rows_stride, int nb,
                              int pollers, int stall_pass, unsigned long long* tpart, hipStream_t s,
                              const PeerRows* peers) {
   int nch = chunk_count(ns);
   if (peers && (peers->n < 0 || peers->n > kMaxPeers || (peers->n > 0 && (!host_rows || !tpart))))
     return hipErrorInvalidValue;  // peer rows go with the tagged tail's host rows only
-  // one shape: 4 waves per CU (the 8-wave shape, 2 waves per SIMD with less residency, measured
-  // 57.7-58.0 vs 50.2-50.3 us per pass, profiles/r03/srv8, is not built)
-  if (nch == 0 || nb <= 0 || waves != 4) return hipErrorInvalidValue;
+  if (nch == 0 || nb <= 0) return hipErrorInvalidValue;
   // a pass completes only when every block has run it, so refuse a grid the device cannot hold at
   // once (one block per CU, at most one per CU by its LDS and registers).  That check is all a
   // cooperative launch adds; the blocks do not synchronise with each other (only with the host's
@@ -4323,22 +3973,22 @@ hipError_t launch_fdf_server(const CorrSoA& c, const uint32_t* ccnt, size_t ns, 
   // cancelled by the host after its deadline -- blocks that start late see the later command at
   // their first gate and exit (pass_gate) -- and the pass re-runs as a launched pass.
   const bool b = bench_passes > 0;
-  const void* fn = b ? reinterpret_cast<const void*>(fdf_server_kernel<true, 4>)
-                     : reinterpret_cast<const void*>(fdf_server_kernel<false, 4>);
+  const void* fn = b ? reinterpret_cast<const void*>(fdf_server_kernel<true, kSrvWaves>)
+                     : reinterpret_cast<const void*>(fdf_server_kernel<false, kSrvWaves>);
   int per_cu = 0, dev = 0, cus = 0;
-  hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64 * waves, 0);
+  hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64 * kSrvWaves, 0);
   if (e == hipSuccess) e = hipGetDevice(&dev);
   if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
   if (e != hipSuccess) return e;
   if (per_cu < 1 || static_cast<long long>(per_cu) * cus < nb) return hipErrorCooperativeLaunchTooLarge;
   PeerRows pr{};
   if (peers) pr = *peers;
-#define MGICP_SRV_LAUNCH(B, W)                                                                                  \
-  fdf_server_kernel<B, W><<<nb, 64 * (W), 0, s>>>(c, ccnt, nch, partial, spart, tickets, out, done_flag, \
+#define MGICP_SRV_LAUNCH(B)                                                                                  \
+  fdf_server_kernel<B, kSrvWaves><<<nb, 64 * kSrvWaves, 0, s>>>(c, ccnt, nch, partial, spart, tickets, out, done_flag, \
                                                   seq0, cmd, mail, timeout_ticks, ptimes, bench_passes, A, host_rows, \
                                                   rows_stride, pollers, stall_pass, tpart, pr)
-  if (b) MGICP_SRV_LAUNCH(true, 4);
-  else MGICP_SRV_LAUNCH(false, 4);
+  if (b) MGICP_SRV_LAUNCH(true);
+  else MGICP_SRV_LAUNCH(false);
 #undef MGICP_SRV_LAUNCH
   return hipGetLastError();
 }
@@ -4585,7 +4235,7 @@ hipError_t preload_kernels(void* pinned, size_t pinned_bytes, hipStream_t s) {
   const void* fns[] = {
       reinterpret_cast<const void*>(&pack_points_kernel),
       reinterpret_cast<const void*>(&bbox_kernel),
-      reinterpret_cast<const void*>(&cell_hist_kernel),
+      reinterpret_cast<const void*>(&cell_keys_kernel),
       reinterpret_cast<const void*>(&cell_sketch_kernel),
       reinterpret_cast<const void*>(&sketch_merge_kernel),
       reinterpret_cast<const void*>(&cell_end_kernel),
@@ -4594,7 +4244,6 @@ hipError_t preload_kernels(void* pinned, size_t pinned_bytes, hipStream_t s) {
       reinterpret_cast<const void*>(&empty_init_kernel),
       reinterpret_cast<const void*>(&empty_pass_kernel),
       reinterpret_cast<const void*>(&iota_kernel),
-      reinterpret_cast<const void*>(&cell_box_kernel),
       reinterpret_cast<const void*>(&knn_cov_kernel<5>),
       reinterpret_cast<const void*>(&knn_cov_kernel<10>),
       reinterpret_cast<const void*>(&knn_cov_kernel<15>),
@@ -4615,17 +4264,14 @@ hipError_t preload_kernels(void* pinned, size_t pinned_bytes, hipStream_t s) {
       reinterpret_cast<const void*>(&knn_cov2_kernel<16>),
       reinterpret_cast<const void*>(&knn_cov2_kernel<24>),
       reinterpret_cast<const void*>(&knn_cov2_kernel<32>),
-      reinterpret_cast<const void*>(&correspond_kernel),
       reinterpret_cast<const void*>(&morton_key_kernel),
       reinterpret_cast<const void*>(&chunk_compact_kernel),
       reinterpret_cast<const void*>(&chunk_compact_list_kernel),
       reinterpret_cast<const void*>(&vl_query_compact_kernel),
       reinterpret_cast<const void*>(&fdf_soa_kernel),
       reinterpret_cast<const void*>(&fdf_soa_gated_kernel),
-      reinterpret_cast<const void*>(&fdf_server_kernel<false, 4>),
-      reinterpret_cast<const void*>(&fdf_server_kernel<true, 4>),
-      reinterpret_cast<const void*>(&fdf_server_kernel<false, 8>),
-      reinterpret_cast<const void*>(&fdf_server_kernel<true, 8>),
+      reinterpret_cast<const void*>(&fdf_server_kernel<false, kSrvWaves>),
+      reinterpret_cast<const void*>(&fdf_server_kernel<true, kSrvWaves>),
       reinterpret_cast<const void*>(&fitness_kernel),
       reinterpret_cast<const void*>(&resolution_kernel),
       reinterpret_cast<const void*>(&radius_keep_kernel),
