@@ -427,8 +427,8 @@ static float* copy_xyz(const float* xyz, size_t n, size_t stride, int* bad) {
 }
 
 int ref_set_source(ref_gicp* g, const float* xyz, size_t n, size_t stride) {
-    free_sum_order(g);  /* a stream order belongs to one source cloud */
     if (!g || (!xyz && n) || stride < 12) return REF_E_INVALID;
+    free_sum_order(g);  /* a stream order belongs to one source cloud */
     int bad;
     free(g->src);
     g->src = copy_xyz(xyz, n, stride, &bad);
