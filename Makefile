@@ -8,7 +8,7 @@ HDRS  := $(wildcard $(PKG)/csrc/*.hpp) include/mi355x_gicp.h
 # -ffp-contract=off: no FMA contraction, so fp32/fp64 expressions round like PCL's SSE2 Eigen
 HIPFLAGS := -O3 -std=c++17 --offload-arch=$(ARCH) -fPIC -ffp-contract=off -Wall -Wno-unused-result
 
-all: $(LIB) oracle adapter-example adapter-replay
+all: $(LIB) oracle adapter-example adapter-replay fod-replay
 
 OBJDIR := $(PKG)/csrc/build
 OBJS  := $(OBJDIR)/mgicp_kernels.o $(OBJDIR)/mgicp_engine.o
@@ -46,6 +46,22 @@ $(REPLAY): adapter/GICPAlignment.cpp adapter/GICPAlignment.h adapter/Filter_mi35
 
 adapter-replay: $(REPLAY)
 
+# adapter/FODDetector_mi355x.cpp (FODDetector::clusterPossibleFODs) compiled the same way, against the
+# stand-ins above plus those of tests/adapter_standins_fod (FODDetector.h, pcl::PointIndices, the members
+# the adapter leaves alone), linked with a replay of test/test_fod_detector.cpp's testFODClustering and
+# testEmptyCloud (test infrastructure)
+STANDIN_FOD := tests/adapter_standins_fod
+FODREPLAY   := adapter/build/replay_test_fod_detector
+$(FODREPLAY): adapter/FODDetector_mi355x.cpp include/mi355x_gicp.h $(wildcard $(STANDIN)/*.h) \
+              $(wildcard $(STANDIN_FOD)/*.h) $(STANDIN)/Utils_standin.cpp $(STANDIN_FOD)/FODDetector_standin.cpp \
+              $(STANDIN_FOD)/replay_test_fod_detector.cpp $(LIB)
+	mkdir -p adapter/build
+	g++ -O2 -std=c++14 -Wall -Wextra -Werror -I$(STANDIN_FOD) -I$(STANDIN) -Iadapter -Iinclude -o $@ \
+	    adapter/FODDetector_mi355x.cpp $(STANDIN)/Utils_standin.cpp $(STANDIN_FOD)/FODDetector_standin.cpp \
+	    $(STANDIN_FOD)/replay_test_fod_detector.cpp -L$(PKG) -lmgicp -Wl,-rpath,'$$ORIGIN/../../$(PKG)'
+
+fod-replay: $(FODREPLAY)
+
 oracle:
 	$(MAKE) -C oracle
 
@@ -53,4 +69,4 @@ clean:
 	rm -f $(LIB) $(PKG)/libmgicp_*.so $(OBJS)
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle clean adapter-example adapter-replay variant
+.PHONY: all oracle clean adapter-example adapter-replay fod-replay variant

@@ -160,6 +160,33 @@ int mgicp_voxel_grid(mgicp_ctx* ctx, const float* in, size_t n, size_t stride, i
                      const double leaf[3], int min_points_per_voxel, float* out, size_t out_stride,
                      size_t* n_out);
 
+/* pcl::EuclideanClusterExtraction<PointXYZRGB>::extract as FODDetector::clusterPossibleFODs calls it
+ * (src/FODDetector.cpp:45-58) on the difference cloud: the connected components of the graph that
+ * links records i != j iff both are finite and FLANN's float d^2 < float(tolerance * tolerance)
+ * (strict, as the radius filter above), found by a lock-free union-find over a grid of cell edge
+ * tolerance / 2 (DESIGN.md "Euclidean clustering").  A component is a cluster iff
+ * max(min_size, 1) <= size <= max_size (max_size = 0: no cap).  Clusters come largest first, equal
+ * sizes by ascending smallest member; members ascending.  float(tolerance^2) = 0 links nothing.
+ * Non-finite records belong to no cluster.  labels[n]: rank of the record's cluster in output order,
+ * -1 none; indices[n]: members, cluster after cluster (the first n_clustered_points entries are
+ * written); offsets[n + 1]: cluster c owns indices[offsets[c] .. offsets[c + 1]), entries past the
+ * last cluster repeat the total.  tolerance negative or NaN: MGICP_E_INVALID; n = 0: no cluster.
+ * Uses the helper cloud slot: a set source / target and their cached state stay as they are.
+ * Single rank: with a communicator attached it runs locally, without a collective. */
+typedef struct {
+    int    n_clusters;         /* reported clusters */
+    int    n_components;       /* components of the finite records before the size filter */
+    double n_clustered_points; /* records in reported clusters */
+    double pair_tests;         /* point-pair distance evaluations the device made */
+    double ms_grid;            /* host call -> grid of the finite records built (upload included) */
+    double ms_device;          /* host clock from the first launch (forest, links, roots, labels, member
+                                  sort; buffers already reserved) to the stream synchronise after the last */
+    double ms_total;           /* host call -> outputs written */
+} mgicp_cluster_info;
+int mgicp_euclidean_clusters(mgicp_ctx* ctx, const float* xyz, size_t n, size_t stride_bytes,
+                             double tolerance, size_t min_size, size_t max_size, int* labels,
+                             int* indices, size_t* offsets, mgicp_cluster_info* info /* may be NULL */);
+
 /* ---- multi-GPU: one process per GPU, point-range shards of the source cloud ----
  * Rank 0 calls mgicp_get_unique_id and broadcasts the 128 bytes out of band (bench.py uses
  * the TCP rendezvous of leica_point_cloud_processing_amd/parallel.py); every rank then calls

@@ -55,6 +55,18 @@ class MgicpResult(ctypes.Structure):
     ]
 
 
+class MgicpClusterInfo(ctypes.Structure):
+    _fields_ = [
+        ("n_clusters", ctypes.c_int),
+        ("n_components", ctypes.c_int),
+        ("n_clustered_points", ctypes.c_double),
+        ("pair_tests", ctypes.c_double),
+        ("ms_grid", ctypes.c_double),
+        ("ms_device", ctypes.c_double),
+        ("ms_total", ctypes.c_double),
+    ]
+
+
 class MgicpError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"mgicp error {code}: {msg}")
@@ -88,6 +100,8 @@ _SIGNATURES = {
                                                   ctypes.POINTER(_SZ)]),
     "mgicp_voxel_grid": (ctypes.c_int, [_P, _P, _SZ, _SZ, ctypes.c_int, _DP, ctypes.c_int, _P, _SZ,
                                          ctypes.POINTER(_SZ)]),
+    "mgicp_euclidean_clusters": (ctypes.c_int, [_P, _P, _SZ, _SZ, ctypes.c_double, _SZ, _SZ, _P, _P, _P,
+                                                 ctypes.POINTER(MgicpClusterInfo)]),
     "mgicp_get_unique_id": (ctypes.c_int, [ctypes.c_char_p]),
     "mgicp_comm_init": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_char_p]),
     "mgicp_comm_attach_shm": (ctypes.c_int, [_P, ctypes.c_char_p, _SZ]),

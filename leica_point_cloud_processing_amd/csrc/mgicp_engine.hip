@@ -41,6 +41,18 @@ constexpr double kDefaultOccupancy = 10.0;          // mean points per non-empty
 constexpr size_t kSmallBytes = size_t(64) << 10;  // pinned readback scratch per context
 constexpr size_t kSketchOffset = size_t(32) << 10;  // the grid sizing sketch's registers in it (16 KiB)
 constexpr size_t kMaxCells = size_t(1) << 29;       // dense cell table cap (2 GiB of uint32)
+// Euclidean clustering's same-cell shortcut: on a grid of edge h = tol / 2 with at most this many cells
+// per axis, any two points of one cell are linked (float d2 < float(tol^2)), so they are united
+// without a distance test.  With u = 2^-24 and H = 1 / inv_h <= h (1 + u): two points of cell c on an
+// axis have fl(fl(v - o) inv_h) in [c, c + 1), so their a = fl(v - o) differ by less than
+// H (1 + 2 (c + 1) u), and v - o = a (1 +- u) with a <= ext; as c H <= ext (1 + 2 u) and
+// ext <= N H for N cells, |v1 - v2| < H (1 + 4 u N + 4 u) <= h (1 + 2^-4 + 2^-21) at N <= 2^18, i.e.
+// < 0.5313 tol.  Exact d^2 < 3 * 0.5313^2 tol^2 < 0.847 tol^2; FLANN's float expression (a rounded
+// difference, three rounded squares, two rounded sums) exceeds the exact value by less than a factor
+// 1 + 2^-21, and float(tol^2) >= tol^2 (1 - u) while it is a normal float: 0.847 (1 + 2^-21) < 1 - u.
+// A grid grown past tol / 2 (kMaxCells), wider than 2^18 cells or with a denormal / infinite
+// float(tol^2) takes the path that tests the pairs inside a cell too.
+constexpr int kCcShortcutMaxDim = 1 << 18;
 // objective-pass launch shape over the fixed reduction tree, A/B-measured on MI355X at 5M points
 // (profiles/r02/ab_tree): 512 persistent 4-wave blocks -- 2 waves per SIMD, so chunk reductions
 // and tickets overlap other waves' streaming (71 us vs 76 us at 256 blocks), and the gated
@@ -275,6 +287,7 @@ struct Cloud {
   bool want_seed_map = false;
   DevBuf<float4> pairs;       // pair-interleaved points (target only: the wave-uniform 1-NN scan)
   bool drop_nonfinite = false; // build the grid over the finite points only (KdTreeFLANN semantics)
+  double force_h = 0.0;        // > 0: build_grid takes this cell edge instead of sizing by occupancy (clustering)
   size_t n_built = 0;          // points of the last grid built in this slot
   bool fresh_grid = false;     // the grid is the one a fresh context builds for these points (target cache)
   DevBuf<double2> cov;        // 3 * cov_stride
@@ -375,6 +388,9 @@ struct mgicp_ctx {
   DevBuf<float4> f_vox, f_vox2;
   DevBuf<unsigned char> f_keep;
   DevBuf<unsigned int> f_count;
+  // Euclidean clustering: the union-find forest, roots, per-root smallest index, sorted members, test counter
+  DevBuf<uint32_t> cc_parent, cc_root, cc_min, cc_members;
+  DevBuf<unsigned long long> cc_tests;
   bool fused_finish = true;              // in-launch reduction finish (debug option "fused_finish")
   double ms_upload_pending = 0;
   // host uploads go through the process-wide HostUploader (host_upload.hpp)
@@ -1125,7 +1141,11 @@ int build_grid(mgicp_ctx* ctx, Cloud& cl, bool defer_extras) {
   // round trip each, two per cloud on a surface: ~0.6-0.8 ms per 5M cloud before the sort)
   const bool fresh = true;
   h = std::max(h, 1e-6);
-  if (maxext > 0.f && n > 1) {
+  if (cl.force_h > 0) {
+    // the caller's cell edge (Euclidean clustering: tolerance / 2), no sketch; at most 2^20 cells per axis
+    // (bcell's clamp), the dense-table cap below may still grow it
+    h = std::max(cl.force_h, static_cast<double>(maxext) / 1048576.0);
+  } else if (maxext > 0.f && n > 1) {
     SketchScales sc;
     double hk[kSketchScales];
     for (int k = 0; k < kSketchScales; ++k) {
@@ -2604,6 +2624,8 @@ void mgicp_destroy(mgicp_ctx* ctx) {
   ctx->f_flags.release(); ctx->f_pos.release(); ctx->f_rgba_in.release(); ctx->f_rgba.release();
   ctx->f_rgba2.release(); ctx->f_vox.release(); ctx->f_vox2.release(); ctx->f_keep.release();
   ctx->f_count.release();
+  ctx->cc_parent.release(); ctx->cc_root.release(); ctx->cc_min.release(); ctx->cc_members.release();
+  ctx->cc_tests.release();
   for (Cloud* c : {&ctx->src, &ctx->tgt, &ctx->aux, &ctx->qry}) {
     c->raw.release(); c->orig.release(); c->pts.release(); c->perm.release();
     c->cell_start.release(); c->cov.release(); c->empty_dist.release(); c->pairs.release();
@@ -2993,6 +3015,108 @@ int mgicp_segment_differences(mgicp_ctx* ctx, const float T_cm[16], const float*
   unsigned int cnt = 0;
   std::memcpy(&cnt, ctx->h_small, sizeof(cnt));
   *n_keep = cnt;
+  return MGICP_OK;
+}
+
+int mgicp_euclidean_clusters(mgicp_ctx* ctx, const float* xyz, size_t n, size_t stride, double tolerance,
+                             size_t min_size, size_t max_size, int* labels, int* indices, size_t* offsets,
+                             mgicp_cluster_info* info) {
+  if (!ctx || !(tolerance >= 0) || !offsets || (n && (!xyz || !labels || !indices))) return MGICP_E_INVALID;
+  HIPCK(hipSetDevice(ctx->device));
+  const double t0 = now_ms();
+  mgicp_cluster_info inf{};
+  if (info) *info = inf;
+  offsets[0] = 0;
+  if (n == 0) return MGICP_OK;
+  int rc = upload_cloud(ctx, ctx->aux, xyz, n, stride, false);
+  if (rc) return rc;
+  std::fill(labels, labels + n, -1);
+  std::fill(offsets, offsets + n + 1, size_t(0));
+  // FLANN's radius: float(tolerance^2), strict.  0 links nothing (not even duplicates): singletons
+  const float r2 = static_cast<float>(tolerance * tolerance);
+  const bool link = r2 > 0.f;
+  // every linked pair lies within `reach` per axis; a denormal r2 may be far above tolerance^2
+  double reach = tolerance;
+  if (r2 < 1.17549435e-38f) reach = std::max(reach, std::sqrt(static_cast<double>(r2)));
+  // non-finite records join no cluster: grid (and forest) over the finite points, label -1 for the rest
+  ctx->aux.drop_nonfinite = true;
+  ctx->aux.force_h = link ? 0.5 * reach : 0.0;
+  rc = build_grid(ctx, ctx->aux);
+  ctx->aux.drop_nonfinite = false;
+  ctx->aux.force_h = 0.0;
+  if (rc) return rc;
+  const double t1 = now_ms();
+  const size_t nf = ctx->aux.n;
+  if (nf == 0) return MGICP_OK;
+  const GridView& g = ctx->aux.view;
+  const bool shortcut = link && r2 >= 1.17549435e-38f && std::isfinite(r2) &&
+                        g.inv_h == static_cast<float>(1.0 / (0.5 * tolerance)) &&
+                        std::max(g.nx, std::max(g.ny, g.nz)) <= kCcShortcutMaxDim;
+  hipStream_t s = ctx->stream;
+  int bits = 1;
+  while ((size_t(1) << bits) < n && bits < 32) ++bits;
+  const size_t sb = sort_scratch_bytes(nf, bits);
+  // the context keeps these buffers between calls (like the grid's scratch)
+  HIPCK(ctx->cc_parent.reserve(nf));
+  HIPCK(ctx->cc_root.reserve(nf));
+  HIPCK(ctx->cc_min.reserve(nf));
+  HIPCK(ctx->cc_members.reserve(nf));
+  HIPCK(ctx->cc_tests.reserve(1));
+  HIPCK(ctx->keys.reserve(nf));
+  HIPCK(ctx->vals.reserve(nf));
+  HIPCK(ctx->scratch.reserve(sb));
+  const double t2 = now_ms();
+  HIPCK(hipMemsetAsync(ctx->cc_tests.p, 0, sizeof(unsigned long long), s));
+  // build_grid left the sorted cell keys of this grid in keys_sorted
+  HIPCK(launch_cc_link(g, nf, ctx->keys_sorted.p, r2, shortcut ? 1 : 0, link ? 1 : 0, ctx->cc_parent.p,
+                       ctx->cc_tests.p, s));
+  HIPCK(launch_cc_labels(g, ctx->aux.perm.p, nf, ctx->cc_parent.p, ctx->cc_root.p, ctx->cc_min.p, ctx->keys.p,
+                         ctx->vals.p, s));
+  // the stable sort by component key over records laid out in original order: members ascending
+  HIPCK(launch_sort_pairs(ctx->scratch.p, sb, ctx->keys.p, ctx->keys_sorted.p, ctx->vals.p, ctx->cc_members.p, nf,
+                          bits, s));
+  if ((rc = sync(ctx))) return rc;
+  const double t3 = now_ms();
+  std::vector<uint32_t> hk(nf), hv(nf);
+  unsigned long long ntests = 0;
+  HIPCK(hipMemcpyAsync(hk.data(), ctx->keys_sorted.p, nf * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  HIPCK(hipMemcpyAsync(hv.data(), ctx->cc_members.p, nf * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  HIPCK(hipMemcpyAsync(&ntests, ctx->cc_tests.p, sizeof(ntests), hipMemcpyDeviceToHost, s));
+  if ((rc = sync(ctx))) return rc;
+  // host finish over the component table: runs of equal keys, in ascending smallest-member order
+  struct Comp { size_t start, size; };
+  std::vector<Comp> kept;
+  const size_t lo = std::max<size_t>(min_size, 1), hi = max_size ? max_size : SIZE_MAX;
+  int ncomp = 0;
+  for (size_t i = 0; i < nf;) {
+    size_t j = i + 1;
+    while (j < nf && hk[j] == hk[i]) ++j;
+    ++ncomp;
+    if (j - i >= lo && j - i <= hi) kept.push_back({i, j - i});
+    i = j;
+  }
+  // PCL: sort(clusters.rbegin(), clusters.rend(), by size) over clusters in ascending-seed order;
+  // documented choice for equal sizes: ascending smallest member
+  std::stable_sort(kept.begin(), kept.end(), [](const Comp& a, const Comp& b) { return a.size > b.size; });
+  size_t off = 0;
+  for (size_t c = 0; c < kept.size(); ++c) {
+    offsets[c] = off;
+    for (size_t m = 0; m < kept[c].size; ++m) {
+      const uint32_t idx = hv[kept[c].start + m];
+      indices[off + m] = static_cast<int>(idx);
+      labels[idx] = static_cast<int>(c);
+    }
+    off += kept[c].size;
+  }
+  for (size_t c = kept.size(); c <= n; ++c) offsets[c] = off;
+  inf.n_clusters = static_cast<int>(kept.size());
+  inf.n_components = ncomp;
+  inf.n_clustered_points = static_cast<double>(off);
+  inf.pair_tests = static_cast<double>(ntests);
+  inf.ms_grid = t1 - t0;
+  inf.ms_device = t3 - t2;
+  inf.ms_total = now_ms() - t0;
+  if (info) *info = inf;
   return MGICP_OK;
 }
 

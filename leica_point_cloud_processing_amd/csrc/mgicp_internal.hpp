@@ -322,6 +322,17 @@ hipError_t launch_voxel_minpts(const float4* vox, const uint32_t* vox_rgba, size
                                uint32_t* flags, uint32_t* pos, void* scratch, size_t scratch_bytes,
                                float4* out, uint32_t* out_rgba, hipStream_t s);
 
+// EuclideanClusterExtraction (FODDetector::clusterPossibleFODs): connected components of "float d2 < r2"
+// over a grid whose cell edge is at least tolerance / 2.  launch_cc_link starts the union-find forest
+// parent[n] (sorted positions) and, with `link`, unites every linked pair; shortcut = 1 promises that
+// any two points of one cell are linked (they are united without a distance test).  *pair_tests
+// (zeroed by the caller) += distance evaluations.  launch_cc_labels then writes, at each point's rank
+// in original order (perm), keys = the smallest original index of its component, vals = its own.
+hipError_t launch_cc_link(const GridView& g, size_t n, const uint32_t* keys_sorted, float r2, int shortcut, int link,
+                          uint32_t* parent, unsigned long long* pair_tests, hipStream_t s);
+hipError_t launch_cc_labels(const GridView& g, const uint32_t* perm, size_t n, uint32_t* parent, uint32_t* root,
+                            uint32_t* min_orig, uint32_t* keys, uint32_t* vals, hipStream_t s);
+
 #if defined(MGICP_CORR_PHASES) && MGICP_CORR_PHASES
 hipError_t corr_phase_take(unsigned long long out[24]);  // diagnostic builds: read and reset
 #endif

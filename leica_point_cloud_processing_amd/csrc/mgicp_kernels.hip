@@ -4201,6 +4201,260 @@ hipError_t launch_voxel_minpts(const float4* vox, const uint32_t* vox_rgba, size
   return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------
+// Euclidean clustering (pcl::EuclideanClusterExtraction as FODDetector::clusterPossibleFODs calls it):
+// connected components of the graph "float d2 < r2" over a grid's points, by a lock-free union-find.
+// ------------------------------------------------------------------------------------
+// parent[] holds sorted positions and only ever decreases: parent[x] <= x at all times (the start value
+// is x or its cell's first position, a hook puts the LARGER root under the smaller one, path halving
+// replaces a parent by the grandparent).  So every walk towards a root strictly descends and ends after
+// at most `depth` steps whatever other waves do meanwhile -- no wave waits for another one.  Other
+// workgroups hook and halve while a walk reads: every read of parent[] in these kernels is a relaxed
+// agent-scope atomic load, every write an atomicCAS / atomicMin.
+__device__ __forceinline__ uint32_t cc_load(const uint32_t* p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// Root of x's tree at some moment during the call.  Being connected is permanent, so two walks that
+// return the same root prove their starts connected; two different roots prove nothing (the caller
+// then tests distances, which is always allowed).
+__device__ __forceinline__ uint32_t cc_find(uint32_t* parent, uint32_t x) {
+  for (;;) {
+    const uint32_t p = cc_load(parent + x);
+    if (p == x) return x;
+    const uint32_t gp = cc_load(parent + p);
+    if (gp != p) atomicMin(parent + x, gp);  // path halving: x is no root and never becomes one again
+    x = gp;
+  }
+}
+
+// A failed CAS means another thread hooked the root `a` since the walk found it; there are at most
+// n - 1 successful hooks in all, so the retries are bounded by the progress of others.
+__device__ __forceinline__ void cc_unite(uint32_t* parent, uint32_t a, uint32_t b) {
+  for (;;) {
+    a = cc_find(parent, a);
+    b = cc_find(parent, b);
+    if (a == b) return;
+    if (a < b) {
+      const uint32_t t = a;
+      a = b;
+      b = t;
+    }
+    if (atomicCAS(parent + a, a, b) == a) return;
+  }
+}
+
+// start of the forest: shortcut grids put every point under its cell's first point (all points of one
+// cell are linked, see kCcShortcutMaxDim in mgicp_engine.hip), the others start as singletons
+__global__ __launch_bounds__(256) void cc_init_kernel(const uint32_t* __restrict__ cell_start,
+                                                      const uint32_t* __restrict__ keys_sorted, size_t n,
+                                                      int shortcut, uint32_t* __restrict__ parent) {
+  const size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  parent[i] = shortcut ? cell_start[keys_sorted[i]] : static_cast<uint32_t>(i);
+}
+
+// Cells whose points can be linked to a point of cell A lie within +-kCcReach cells of A on every axis:
+// linked points differ by less than tol (1 + 2^-22) per axis, the grid's h is at least tol / 2 (1 - 2^-24),
+// so their exact cell coordinates differ by less than 2.001; bcell's float value of a coordinate
+// below 2^20 (its clamp, which like floor is monotone and never widens a difference) is off by at most
+// 3 * 2^-24 * 2^20 < 0.19 cells, and floor(a) - floor(b) < a - b + 1 < 3.4.  +-2 would need exact cell
+// arithmetic: a pair 2.0001 cells apart may straddle three cell borders.
+constexpr int kCcReach = 3;
+constexpr int kCcSpan = 2 * kCcReach + 1;
+constexpr int kCcSelf = (kCcSpan * kCcSpan * kCcSpan - 1) / 2;  // the centre of the offset cube
+
+// bounding box of the points [p0, p1) by one whole wave (every lane gets it)
+__device__ __forceinline__ void cc_bbox(const float4* __restrict__ pts, uint32_t p0, uint32_t p1, int lane,
+                                        float (&lo)[3], float (&hi)[3]) {
+  lo[0] = lo[1] = lo[2] = INFINITY;
+  hi[0] = hi[1] = hi[2] = -INFINITY;
+  for (uint32_t j = p0 + static_cast<uint32_t>(lane); j < p1; j += 64) {
+    const float4 p = pts[j];
+    lo[0] = fminf(lo[0], p.x); lo[1] = fminf(lo[1], p.y); lo[2] = fminf(lo[2], p.z);
+    hi[0] = fmaxf(hi[0], p.x); hi[1] = fmaxf(hi[1], p.y); hi[2] = fmaxf(hi[2], p.z);
+  }
+#pragma unroll
+  for (int m = 32; m > 0; m >>= 1) {
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      lo[d] = fminf(lo[d], __shfl_xor(lo[d], m));
+      hi[d] = fmaxf(hi[d], __shfl_xor(hi[d], m));
+    }
+  }
+}
+
+// No point of box A links to a point of box B: along an axis every pair differs by at least the
+// boxes' gap g (exactly, as real numbers), FLANN's float d2 of the pair is at least
+// (gx^2 + gy^2 + gz^2) (1 - 2^-21) (a rounded difference, three rounded squares, two rounded sums),
+// and the float G below is within 2^-21 of that sum too; the 1e-5 margin covers both.  Squares that
+// underflow only lower G (no prune); an overflowing G means every pair's d2 overflows as well.
+__device__ __forceinline__ bool cc_boxes_apart(const float (&alo)[3], const float (&ahi)[3], const float (&blo)[3],
+                                               const float (&bhi)[3], float r2) {
+  float G = 0.f;
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    const float g = fmaxf(fmaxf(blo[d] - ahi[d], alo[d] - bhi[d]), 0.f);
+    G = G + g * g;
+  }
+  return G * 0.99999f >= r2;
+}
+// "Are the cells that start at a and b one component already?", decided ONCE per wave: lane 0 walks
+// and its answer is broadcast.  Lanes that walked on their own could read different values of a
+// parent[] entry that another workgroup is hooking at that moment and disagree; the wave-wide
+// ballots, shuffles and box reductions that follow need every lane on the same branch.
+__device__ __forceinline__ bool cc_cells_joined(uint32_t* parent, uint32_t a, uint32_t b, int lane) {
+  int same = 0;
+  if (lane == 0) same = cc_find(parent, a) == cc_find(parent, b) ? 1 : 0;
+  return __builtin_amdgcn_readfirstlane(same) != 0;
+}
+// a value every lane holds alike (it came out of a shuffle from one lane), told to the compiler
+__device__ __forceinline__ uint32_t cc_uniform(uint32_t v) {
+  return static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(v)));
+}
+constexpr uint32_t kCcBoxMinPairs = 4096;  // point pairs from which a pair of cells is worth the two box passes
+
+// One wave per 64 sorted positions; the wave serves the cells that START in its range, one after the
+// other.  For cell A it visits each non-empty cell B after A in linear order inside the reach (every
+// unordered pair of cells once), and A itself on grids without the shortcut.
+//   shortcut: a cell is wholly one component, so a pair of cells whose first points have one root is
+//     skipped (asked again before every slab of 64 x |smaller cell| tests), and the point pairs of the
+//     others are tested only up to the first link.
+//   otherwise: every point pair of A x B (and i < j of A x A) is tested and every link united.
+// Lanes hold 64 points of the larger cell, the smaller cell's points are broadcast one by one.
+// Every branch around a wave-wide operation (ballot, shuffle, the box reductions) is taken on a value
+// that is one per wave: cell bounds pass through cc_uniform, the root comparison through
+// cc_cells_joined, `linked` and `have_abox` follow from ballots and those; only the unite calls diverge.
+// *pair_tests += distance evaluations (one integer atomic per wave).
+__global__ __launch_bounds__(256) void cc_link_kernel(GridView g, size_t n, const uint32_t* __restrict__ keys_sorted,
+                                                      float r2, int shortcut, uint32_t* __restrict__ parent,
+                                                      unsigned long long* __restrict__ pair_tests) {
+  const int lane = threadIdx.x & 63;
+  const size_t base = (static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x) & ~static_cast<size_t>(63);
+  if (base >= n) return;  // whole wave
+  const size_t i = base + lane;
+  const uint32_t key = i < n ? keys_sorted[i] : 0u;
+  const bool head = i < n && (i == 0 || keys_sorted[i - 1] != key);
+  unsigned long long heads = __ballot(head);
+  unsigned long long tests = 0;
+  const uint32_t nx = static_cast<uint32_t>(g.nx), ny = static_cast<uint32_t>(g.ny);
+  while (heads) {
+    const int hl = __ffsll(static_cast<long long>(heads)) - 1;
+    heads &= heads - 1;
+    const uint32_t ka = cc_uniform(static_cast<uint32_t>(__shfl(static_cast<int>(key), hl)));
+    const uint32_t a0 = g.cell_start[ka], a1 = g.cell_start[ka + 1];
+    const int ax = static_cast<int>(ka % nx), ay = static_cast<int>((ka / nx) % ny), az = static_cast<int>(ka / (nx * ny));
+    float alo[3] = {0.f, 0.f, 0.f}, ahi[3] = {0.f, 0.f, 0.f};
+    bool have_abox = false;
+    for (int t0 = kCcSelf; t0 < kCcSpan * kCcSpan * kCcSpan; t0 += 64) {
+      const int t = t0 + lane;
+      uint32_t b0 = 0, b1 = 0, kb = 0;
+      if (t < kCcSpan * kCcSpan * kCcSpan && (t > kCcSelf || !shortcut)) {
+        const int bx = ax + t % kCcSpan - kCcReach, by = ay + (t / kCcSpan) % kCcSpan - kCcReach,
+                  bz = az + t / (kCcSpan * kCcSpan) - kCcReach;
+        if (bx >= 0 && by >= 0 && bz >= 0 && bx < g.nx && by < g.ny && bz < g.nz) {
+          kb = static_cast<uint32_t>(bx) + nx * (static_cast<uint32_t>(by) + ny * static_cast<uint32_t>(bz));
+          b0 = g.cell_start[kb];
+          b1 = g.cell_start[kb + 1];
+        }
+      }
+      unsigned long long cand = __ballot(b1 > b0);
+      while (cand) {
+        const int cl = __ffsll(static_cast<long long>(cand)) - 1;
+        cand &= cand - 1;
+        const uint32_t c0 = cc_uniform(static_cast<uint32_t>(__shfl(static_cast<int>(b0), cl)));
+        const uint32_t c1 = cc_uniform(static_cast<uint32_t>(__shfl(static_cast<int>(b1), cl)));
+        const bool self = cc_uniform(static_cast<uint32_t>(__shfl(static_cast<int>(kb), cl))) == ka;
+        if (shortcut && cc_cells_joined(parent, a0, c0, lane)) continue;
+        // populous pairs: skipped when their points' bounding boxes are already too far apart (most
+        // cells at the rim of the reach are)
+        if (!self && static_cast<unsigned long long>(a1 - a0) * (c1 - c0) >= kCcBoxMinPairs) {
+          if (!have_abox) {
+            cc_bbox(g.pts, a0, a1, lane, alo, ahi);
+            have_abox = true;
+          }
+          float blo[3], bhi[3];
+          cc_bbox(g.pts, c0, c1, lane, blo, bhi);
+          if (cc_boxes_apart(alo, ahi, blo, bhi, r2)) continue;
+        }
+        // lanes over the larger cell [l0, l1), the smaller one [s0, s1) broadcast
+        const bool a_large = a1 - a0 >= c1 - c0;
+        const uint32_t l0 = a_large ? a0 : c0, l1 = a_large ? a1 : c1;
+        const uint32_t s0 = a_large ? c0 : a0, s1 = a_large ? c1 : a1;
+        bool linked = false;
+        for (uint32_t lb = l0; lb < l1 && !linked; lb += 64) {
+          // other waves may have joined the two cells meanwhile: look again before each slab of tests
+          if (shortcut && lb != l0 && cc_cells_joined(parent, a0, c0, lane)) break;
+          const uint32_t j = lb + static_cast<uint32_t>(lane);
+          const bool have = j < l1;
+          const float4 pj = g.pts[have ? j : l0];
+          for (uint32_t k = s0; k < s1; ++k) {
+            const float4 pk = g.pts[k];  // one address for the whole wave
+            const bool valid = have && (!self || j > k);
+            const bool hit = valid && dist2(pk.x, pk.y, pk.z, pj) < r2;
+            tests += static_cast<unsigned long long>(__popcll(__ballot(valid)));
+            const unsigned long long hits = __ballot(hit);
+            if (!hits) continue;
+            if (shortcut) {  // the two cells are one component from here on
+              if (lane == __ffsll(static_cast<long long>(hits)) - 1) cc_unite(parent, j, k);
+              linked = true;
+              break;
+            }
+            if (hit) cc_unite(parent, j, k);
+          }
+        }
+      }
+    }
+  }
+  if (lane == 0 && tests) atomicAdd(pair_tests, tests);
+}
+
+// pointer jumping to the root of every point (the forest no longer changes, other threads still halve
+// paths: atomic reads), and the component's smallest original index by an integer atomicMin at its root
+__global__ __launch_bounds__(256) void cc_root_kernel(const float4* __restrict__ pts, size_t n, uint32_t* __restrict__ parent,
+                                                      uint32_t* __restrict__ root, uint32_t* __restrict__ min_orig) {
+  const size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t r = cc_find(parent, static_cast<uint32_t>(i));
+  root[i] = r;
+  atomicMin(min_orig + r, __float_as_uint(pts[i].w));
+}
+
+// (component's smallest original index, original index) of every point, written at the point's rank in
+// ORIGINAL order (perm: sorted position -> that rank), so a stable sort by the key leaves each
+// component's members ascending
+__global__ __launch_bounds__(256) void cc_emit_kernel(const float4* __restrict__ pts, const uint32_t* __restrict__ perm,
+                                                      size_t n, const uint32_t* __restrict__ root,
+                                                      const uint32_t* __restrict__ min_orig, uint32_t* __restrict__ keys,
+                                                      uint32_t* __restrict__ vals) {
+  const size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t c = perm[i];
+  keys[c] = min_orig[root[i]];
+  vals[c] = __float_as_uint(pts[i].w);
+}
+
+hipError_t launch_cc_link(const GridView& g, size_t n, const uint32_t* keys_sorted, float r2, int shortcut, int link,
+                          uint32_t* parent, unsigned long long* pair_tests, hipStream_t s) {
+  if (!n) return hipSuccess;
+  cc_init_kernel<<<nblk(n), 256, 0, s>>>(g.cell_start, keys_sorted, n, shortcut, parent);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess || !link) return e;
+  cc_link_kernel<<<nblk(n), 256, 0, s>>>(g, n, keys_sorted, r2, shortcut, parent, pair_tests);
+  return hipGetLastError();
+}
+
+hipError_t launch_cc_labels(const GridView& g, const uint32_t* perm, size_t n, uint32_t* parent, uint32_t* root,
+                            uint32_t* min_orig, uint32_t* keys, uint32_t* vals, hipStream_t s) {
+  if (!n) return hipSuccess;
+  hipError_t e = hipMemsetAsync(min_orig, 0xff, n * sizeof(uint32_t), s);
+  if (e != hipSuccess) return e;
+  cc_root_kernel<<<nblk(n), 256, 0, s>>>(g.pts, n, parent, root, min_orig);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  cc_emit_kernel<<<nblk(n), 256, 0, s>>>(g.pts, perm, n, root, min_orig, keys, vals);
+  return hipGetLastError();
+}
+
 size_t sort_scratch_bytes(size_t n, int bits) {
   size_t bytes = 0;
   (void)hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, static_cast<const uint32_t*>(nullptr),
@@ -4290,6 +4544,10 @@ hipError_t preload_kernels(void* pinned, size_t pinned_bytes, hipStream_t s) {
       reinterpret_cast<const void*>(&voxel_centroid_kernel),
       reinterpret_cast<const void*>(&voxel_minpts_kernel),
       reinterpret_cast<const void*>(&scatter_voxels_kernel),
+      reinterpret_cast<const void*>(&cc_init_kernel),
+      reinterpret_cast<const void*>(&cc_link_kernel),
+      reinterpret_cast<const void*>(&cc_root_kernel),
+      reinterpret_cast<const void*>(&cc_emit_kernel),
   };
   for (const void* f : fns) {
     hipFuncAttributes attr;

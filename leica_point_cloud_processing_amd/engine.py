@@ -261,6 +261,27 @@ class GICPEngine:
             ns, ssub, float(sqr_threshold), keep.ctypes.data, ctypes.byref(cnt)), "segment_differences")
         return keep[:n].astype(bool), int(cnt.value)
 
+    def euclidean_clusters(self, cloud, tolerance: float, min_size: int = 1, max_size: int = 0):
+        """pcl::EuclideanClusterExtraction (FODDetector::clusterPossibleFODs): (clusters, labels, info).
+        `clusters`: int32 index arrays, largest first (equal sizes by smallest member), members
+        ascending; `labels`: per record the rank of its cluster or -1; `info`: the call's counters."""
+        min_size, max_size = int(min_size), int(max_size)
+        if min_size < 0 or max_size < 0:  # would wrap to a huge size_t
+            raise ValueError(f"euclidean_clusters: min_size {min_size} / max_size {max_size} must be >= 0")
+        _keep, ptr, n, stride = self._cloud_arg(cloud)
+        labels = np.full(max(n, 1), -1, np.int32)
+        indices = np.zeros(max(n, 1), np.int32)
+        offsets = np.zeros(n + 1, np.uintp)
+        ci = _lib.MgicpClusterInfo()
+        self._check(self._lib.mgicp_euclidean_clusters(
+            self._h, ctypes.c_void_p(ptr), n, stride, float(tolerance), int(min_size), int(max_size),
+            labels.ctypes.data, indices.ctypes.data, offsets.ctypes.data, ctypes.byref(ci)), "euclidean_clusters")
+        off = offsets.astype(np.int64)
+        clusters = [indices[off[c]:off[c + 1]].copy() for c in range(ci.n_clusters)]
+        info = {f: getattr(ci, f) for f, _ in ci._fields_}
+        info["offsets"] = off[:ci.n_clusters + 1]
+        return clusters, labels[:n], info
+
     def voxel_grid(self, cloud: PointCloudRGB, leaf, min_points_per_voxel: int = 0) -> PointCloudRGB:
         """pcl::VoxelGrid<PointXYZRGB>::filter (Filter::downsampleCloud) -> a new cloud."""
         from .cloud import POINT_XYZRGB
