@@ -1,4 +1,4 @@
-"""ctypes binding of libmgicp.so (include/mi355x_gicp.h).
+"""ctypes binding of libmgicp.so (include/mi355x_gicp.h and, for tests and bench.py, mi355x_gicp_debug.h).
 
 The HIP engine is the only compute path of this package: if the in-tree library is missing
 or cannot be loaded, every entry point raises immediately -- there is no CPU fallback.
@@ -11,7 +11,8 @@ import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, os.environ.get("MGICP_LIB_NAME", "libmgicp.so"))  # variant builds for A/B
-HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mi355x_gicp.h")
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mi355x_gicp.h")  # the product (drop-in) calls
+DEBUG_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mi355x_gicp_debug.h")  # test / bench hooks
 
 MGICP_OK = 0
 MGICP_E_INVALID = -1
@@ -134,10 +135,13 @@ _SIGNATURES = {
 _lib = None
 
 
-def header_symbols(path: str = HEADER_PATH) -> list[str]:
-    """Every function declared in include/mi355x_gicp.h."""
+def header_symbols(path: str | None = None) -> list[str]:
+    """Every function one header declares; without a path, the union of the product header
+    (include/mi355x_gicp.h) and the debug header (include/mi355x_gicp_debug.h): all the library exports."""
+    if path is None:
+        return sorted(set(header_symbols(HEADER_PATH)) | set(header_symbols(DEBUG_HEADER_PATH)))
     with open(path) as f:
-        text = f.read()
+        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)  # declarations only: the docs name other calls
     return sorted(set(re.findall(r"\b(mgicp_[a-z_0-9]+)\s*\(", text)))
 
 

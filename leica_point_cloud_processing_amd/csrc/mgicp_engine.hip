@@ -26,14 +26,17 @@
 #include <thread>
 #include <vector>
 
-#include "../../include/mi355x_gicp.h"
 #include "host_upload.hpp"
-#include "mgicp_internal.hpp"
+#include "mgicp_ctx.hpp"
 #include "gn_solver.hpp"
-#include "pcl_bfgs.hpp"
-#include "shm_rows.hpp"
 
 using namespace mgicp;
+
+// Helpers defined below as mgicp::name are declared in mgicp_ctx.hpp: the debug entry points
+// (mgicp_debug.hip) call them too.  Everything else stays in this file's anonymous namespace.
+bool (*mgicp::g_oom_evict)() = nullptr;
+thread_local Graveyard* mgicp::t_new_ctx_grave = nullptr;
+TargetCache mgicp::g_tcache[64];  // r05 target cache: one entry per device
 
 namespace {
 
@@ -53,12 +56,6 @@ constexpr size_t kMaxCells = size_t(1) << 29;       // dense cell table cap (2 G
 // A grid grown past tol / 2 (kMaxCells), wider than 2^18 cells or with a denormal / infinite
 // float(tol^2) takes the path that tests the pairs inside a cell too.
 constexpr int kCcShortcutMaxDim = 1 << 18;
-// objective-pass launch shape over the fixed reduction tree, A/B-measured on MI355X at 5M points
-// (profiles/r02/ab_tree): 512 persistent 4-wave blocks -- 2 waves per SIMD, so chunk reductions
-// and tickets overlap other waves' streaming (71 us vs 76 us at 256 blocks), and the gated
-// grid (134 VGPRs: 3 waves per SIMD) stays resident while it waits at the gate (14.5 ms per C4
-// align vs 14.9 ms at 1024 blocks); in-launch finish
-constexpr int kFdfMaxBlocks = 512;
 // objective-pass event sampling while profiling: every 8th launch (identical work per launch, and two
 // event records per pass would cost ~4 % of the PCL-mode align)
 constexpr unsigned kProfStride = 8;
@@ -71,10 +68,6 @@ double now_ms() {
              std::chrono::steady_clock::now().time_since_epoch())
       .count();
 }
-
-#ifndef MGICP_PASS_DIAG
-#define MGICP_PASS_DIAG 0
-#endif
 
 // MGICP_TRACE=1: phase timestamps of uploads and grid builds on stderr (host-time diagnosis)
 bool trace_on() {
@@ -91,36 +84,6 @@ bool knn_stats_on() { return std::getenv("MGICP_KNN_STATS") != nullptr; }
   do {                                                                         \
     if (trace_on()) std::fprintf(stderr, "[mgicp] %10.3f ms  %s\n", now_ms(), label); \
   } while (0)
-
-struct Mat4 {  // row-major float 4x4
-  float m[4][4];
-  static Mat4 identity() {
-    Mat4 r;
-    std::memset(r.m, 0, sizeof(r.m));
-    r.m[0][0] = r.m[1][1] = r.m[2][2] = r.m[3][3] = 1.f;
-    return r;
-  }
-  static Mat4 from_cm(const float* cm) {
-    Mat4 r;
-    for (int i = 0; i < 4; ++i)
-      for (int j = 0; j < 4; ++j) r.m[i][j] = cm[j * 4 + i];
-    return r;
-  }
-  void to_cm(float* cm) const {
-    for (int i = 0; i < 4; ++i)
-      for (int j = 0; j < 4; ++j) cm[j * 4 + i] = m[i][j];
-  }
-  bool is_identity() const {
-    const Mat4 I = identity();
-    return std::memcmp(m, I.m, sizeof(m)) == 0;
-  }
-  Xf34 xf() const {
-    Xf34 x;
-    for (int i = 0; i < 3; ++i)
-      for (int j = 0; j < 4; ++j) x.m[4 * i + j] = m[i][j];
-    return x;
-  }
-};
 
 // GICP::applyState(t = I, x): R = AngleAxisf(x5,Z) * AngleAxisf(x4,Y) * AngleAxisf(x3,X)
 // evaluated through Eigen's quaternion products, then t.col(3) += (x0, x1, x2, 0).
@@ -148,7 +111,8 @@ Quat quat_mul(const Quat& a, const Quat& b) {
   r.z = a.w * b.z + a.z * b.w + a.x * b.y - a.y * b.x;
   return r;
 }
-Mat4 apply_state(const Vec6& x) {
+}  // namespace
+Mat4 mgicp::apply_state(const Vec6& x) {
   const Quat q = quat_mul(quat_mul(quat_axis(static_cast<float>(x[5]), 2),
                                    quat_axis(static_cast<float>(x[4]), 1)),
                           quat_axis(static_cast<float>(x[3]), 0));
@@ -171,6 +135,7 @@ Mat4 apply_state(const Vec6& x) {
   T.m[2][3] = 0.0f + static_cast<float>(x[2]);
   return T;
 }
+namespace {
 
 // GICP::computeRDerivative + matricesInnerProd (tr(dR * Rsum))
 void r_derivative(const Vec6& x, const double R[3][3], Vec6& g) {
@@ -216,104 +181,6 @@ void r_derivative(const Vec6& x, const double R[3][3], Vec6& g) {
   }
 }
 
-// Device buffers a reserve() replaces are freed at quiet points of their OWN context (the end of an
-// align, a destroy), not at once: hipFree waits for the whole device, which stalled set_*'s grid build
-// behind the other cloud's covariance head start on the second stream (r04, ~2 ms, profiles/r04/prep7).
-// One graveyard per context: a context's quiet point never frees -- and so never waits
-// on -- buffers of another context or device.
-struct Graveyard {
-  std::vector<void*> v;
-  void flush() {
-    for (void* p : v) (void)hipFree(p);
-    v.clear();
-  }
-};
-// r06: a device allocation that fails for lack of memory first evicts the process-wide
-// target cache's entry of the current device (set below, next to the cache) and retries once
-bool (*g_oom_evict)() = nullptr;
-// the graveyard of the context being constructed: every DevBuf member of a mgicp_ctx picks it up
-thread_local Graveyard* t_new_ctx_grave = nullptr;
-
-template <class T>
-struct DevBuf {
-  T* p = nullptr;
-  size_t cap = 0;
-  Graveyard* grave = t_new_ctx_grave;
-  bool fine = false;  // fine-grained device memory (r06: the xGMI exchange rows, which peers store into)
-  // grows by >= 1/4 so that a sequence of slightly larger requests (grid sizing iterations,
-  // the second cloud) does not pay a hipFree/hipMalloc pair each time
-  hipError_t reserve(size_t n) {
-    if (n <= cap && p) return hipSuccess;
-    const size_t want = std::max<size_t>(std::max<size_t>(n, 1), cap ? cap + cap / 4 : 0);
-    if (p) {
-      if (grave) grave->v.push_back(p);
-      else (void)hipFree(p);
-    }
-    p = nullptr;
-    cap = 0;
-    auto alloc = [&]() {
-      return fine ? hipExtMallocWithFlags(reinterpret_cast<void**>(&p), want * sizeof(T), hipDeviceMallocFinegrained)
-                  : hipMalloc(&p, want * sizeof(T));
-    };
-    hipError_t e = alloc();
-    if (e == hipErrorOutOfMemory && g_oom_evict) {
-      (void)hipGetLastError();
-      p = nullptr;
-      if (g_oom_evict()) e = alloc();
-    }
-    if (e == hipSuccess) cap = want;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-};
-
-struct Cloud {
-  size_t n = 0;
-  bool dirty = false;      // grid must be rebuilt
-  bool have_cov = false;   // covariances valid for [cov_p0, cov_p1)
-  size_t cov_p0 = 0, cov_p1 = 0;
-  DevBuf<unsigned char> raw;  // staging of strided records
-  DevBuf<float4> orig;        // original order, w = index
-  DevBuf<float4> pts;         // grid-sorted
-  DevBuf<uint32_t> perm;      // sorted pos -> original index
-  DevBuf<uint32_t> cell_start;
-  DevBuf<uint8_t> empty_dist; // empty-space map (target only: 1-NN queries leave the surface)
-  bool want_empty_map = false;
-  DevBuf<uint32_t> seed, seed_scratch;  // seed map (target: first-sweep 1-NN seeds)
-  bool want_seed_map = false;
-  DevBuf<float4> pairs;       // pair-interleaved points (target only: the wave-uniform 1-NN scan)
-  bool drop_nonfinite = false; // build the grid over the finite points only (KdTreeFLANN semantics)
-  double force_h = 0.0;        // > 0: build_grid takes this cell edge instead of sizing by occupancy (clustering)
-  size_t n_built = 0;          // points of the last grid built in this slot
-  bool fresh_grid = false;     // the grid is the one a fresh context builds for these points (target cache)
-  DevBuf<double2> cov;        // 3 * cov_stride
-  size_t cov_stride = 0;      // entries per covariance array (n, or the padded all-gather size)
-  float lo[3] = {0.f, 0.f, 0.f}, hi[3] = {0.f, 0.f, 0.f};  // bounding box (original coordinates)
-  GridView view{};
-  size_t ncells = 0;
-  Cov3 cov3() const { return Cov3{cov.p, cov.p + cov_stride, cov.p + 2 * cov_stride}; }
-};
-
-enum { kFamCov = 0, kFamCorr = 1, kFamFdf = 2, kFamRed = 3, kFamCompact = 4, kFamMoments = 5, kFams = 6 };
-
-// pass-path counters (mgicp_debug_pass_stats)
-enum {
-  kStSrvLaunch = 0,  // resident servers launched
-  kStSrvPass,        // objective passes run by a server
-  kStLaunchedPass,   // objective passes run by a launched kernel (gated, plain, or taking over)
-  kStTakeover,       // server passes that missed their deadline and were re-run as launched passes
-  kStBar,            // 1: the server reads its commands from device memory written through the BAR
-  kStRowsAlloc,      // private host-row buffer allocations
-  kStTransport,      // 0 local, 1 RCCL, 2 shared segment, 3 shared segment + RCCL (bulk all-gathers),
-                     // 4 xGMI row exchange (+ segment), 5 xGMI row exchange + RCCL
-  kStSrvDenied,      // server launches refused because another context of this process held the device
-  kStCount
-};
-
 // One resident server per device and process: its blocks need every CU of the device (one block
 // per CU, 512 registers per lane), so a second context aligning on the same device at the same
 // time runs launched passes instead of a second server.
@@ -324,25 +191,6 @@ void swap_buf(DevBuf<T>& a, DevBuf<T>& b) {  // the device memory changes hands;
   std::swap(a.p, b.p);
   std::swap(a.cap, b.cap);
 }
-
-// r05 target cache: one entry per device (its DevBufs belong to no context: grave = nullptr)
-struct TargetCache {
-  std::mutex mu;
-  bool valid = false;
-  Cloud t;
-  int k = 0;
-  double eps = 0;
-  bool vl_valid = false, vl_alloc = false, vl_off = false;
-  VListView vl{};
-  size_t vl_ncells = 0;
-  uint32_t vl_epoch = 0;
-  int vl_groups = 0;
-  DevBuf<uint32_t> vl_cell;
-  DevBuf<float4> vl_pool;
-  DevBuf<unsigned int> vl_ctr;
-  long long hits = 0, donations = 0;
-};
-TargetCache g_tcache[64];
 
 // the target's device state: every buffer a grid, its covariances and its cell lists live in
 template <class F>
@@ -371,266 +219,6 @@ bool tcache_evict_current() {
 struct OomHookInit {
   OomHookInit() { g_oom_evict = &tcache_evict_current; }
 } g_oom_hook_init;
-
-}  // namespace
-
-struct mgicp_ctx {
-  std::unique_ptr<Graveyard> grave;  // replaced device buffers of THIS context, freed at its quiet points
-  mgicp_params prm{};
-  std::string err;
-  int device = 0;
-  hipStream_t stream = nullptr;
-  Cloud src, tgt;
-  Cloud aux;  // scratch cloud of the resolution / radius / segment-differences helpers
-  Cloud qry;  // query points of the FOD-side helpers (packed only, no grid)
-  // FOD-side helper buffers (SegmentDifferences, VoxelGrid)
-  DevBuf<uint32_t> f_flags, f_pos, f_rgba_in, f_rgba, f_rgba2;
-  DevBuf<float4> f_vox, f_vox2;
-  DevBuf<unsigned char> f_keep;
-  DevBuf<unsigned int> f_count;
-  // Euclidean clustering: the union-find forest, roots, per-root smallest index, sorted members, test counter
-  DevBuf<uint32_t> cc_parent, cc_root, cc_min, cc_members;
-  DevBuf<unsigned long long> cc_tests;
-  bool fused_finish = true;              // in-launch reduction finish (debug option "fused_finish")
-  double ms_upload_pending = 0;
-  // host uploads go through the process-wide HostUploader (host_upload.hpp)
-  int host_threads = 8;                  // packing workers (fixed)
-  DevBuf<float> xyz_dev;                 // packed xyz landing zone
-  // per source point (sorted), rank shard only
-  DevBuf<float4> src_out;  // guess-applied source (only when guess != I)
-  const float4* d_out = nullptr;
-  // compacted accepted correspondences of the current outer iteration (shard-relative)
-  DevBuf<uint32_t> prev_pos;  // matched target sorted position per shard point (also the next 1-NN seed)
-  DevBuf<uint32_t> flags;
-  DevBuf<float> corr_f;    // 6 streams
-  DevBuf<double> corr_d;   // 6 streams
-
-  size_t corr_cap = 0;     // elements per stream (multiple of 4)
-  bool seed_valid = false;
-  // query order of the 1-NN sweeps (Morton order of the shard)
-  bool qperm_valid = false;
-  DevBuf<uint32_t> qperm;
-  // the fixed reduction tree (internal.hpp kChunkPts / kSuperChunks): chunk layout of the streams,
-  // chunk and super partials of this shard, the all-gathered supers of every rank, the total
-  DevBuf<uint32_t> ccnt;  // chunk_count(ns): correspondences per chunk (fixed-slot layout, r04)
-  DevBuf<double> partial;       // chunk partials, kRedVals each
-  DevBuf<unsigned long long> tpart;  // the server's stamped chunk partials, 32 words each (r03; 0xff.. = no stamp)
-  size_t tpart_n = 0;
-  DevBuf<double> spart;         // super partials (max_supers() rows: the all-gather send size)
-  DevBuf<double> gath;          // nranks x max_supers() rows
-  DevBuf<double> red;           // kRedVals
-  DevBuf<unsigned int> tickets; // per super + 1: arrival counters of the in-launch finish
-  size_t tickets_n = 0;
-  // Gauss-Newton mode: chunk / super partials and the totals of one pass, and their host copy
-  DevBuf<double> mpartial, msuper, mred;
-  double mom[kMomVals] = {};
-  double out_ctr[3] = {0, 0, 0};  // moment expansion centre: bbox midpoint of the guess-applied source
-  unsigned char* h_small = nullptr;  // pinned, mapped host scratch (kSmallBytes) for small readbacks
-  unsigned char* d_small = nullptr;  // its device address (kernels write results there directly)
-  double* h_red = nullptr;   // pinned, mapped, coherent host memory
-  double* d_h_red = nullptr; // its device address
-  unsigned long long* h_flag = nullptr;  // pass-completion word (host / device views)
-  unsigned long long* d_flag = nullptr;
-  unsigned long long pass_seq = 0;
-  // pre-launched (gated) objective passes: pass k + 1 is queued while pass k runs and waits on the
-  // host-written command block (debug option "gated"; single-GPU polled mode)
-  bool gated = true;
-  PassCmd* h_cmd = nullptr;             // pinned, mapped, coherent host memory
-  PassCmd* d_cmd = nullptr;             // its device address
-  PassCmd* mail = nullptr;              // device copy block 0 of a gated pass forwards to the others
-  // the server's command block in fine-grained device memory that the host stores into through the
-  // BAR (debug option "bar_cmd"): every server block polls it, no PCIe read and no mailbox hop
-  bool bar = true;
-  PassCmd* bar_cmd = nullptr;
-  // MGICP_PASS_DIAG builds: per gated pass (seq & 1023) the device wall clock at kernel start, command
-  // seen, last block through the gate; the host's wall clock (us) at flag seen / command published
-  unsigned long long* h_gtrace = nullptr;  // mapped host memory, 4 x 1024
-  unsigned long long* d_gtrace = nullptr;
-  std::vector<double> host_gt;             // 2 x 1024
-  unsigned long long gated_seq = 0;     // sequence number of the queued gated pass (0 = none)
-  unsigned long long gate_timeout = 0;  // wall_clock64 ticks a gated pass waits before giving up
-  // the resident pass server (debug option "resident"; single GPU polled mode, or any rank count with the
-  // shared row segment): one launch per BFGS run keeps part of the compacted streams in registers /
-  // LDS across all its passes
-  bool resident = true;
-  bool srv_live = false;                // a server is running and waits for pass srv_next
-  bool srv_locked = false;              // this context holds g_srv_busy[device]
-  bool srv_degraded = false;            // a server pass was taken over: launched passes until the align ends
-  unsigned long long srv_next = 0;
-  int cus = 0;                          // compute units (the server's grid)
-  int srv_cus = 0;                      // debug option "srv_cus": cap on the server's blocks (0 = every CU)
-  int stall_pass = -1;                  // env MGICP_SRV_STALL_PASS (tests): a server block withholds this pass
-  int quit_pass = -1;                   // env MGICP_DEBUG_QUIT_PASS (tests): the host gives up at this pass index
-                                        // with MGICP_E_COMM (a rank that dies mid-align, seen from the others)
-  double row_deadline_ms = 500.0;       // env MGICP_ROW_DEADLINE_MS: own rows missing this long -> take over
-  double remote_deadline_s = 120.0;     // env MGICP_REMOTE_DEADLINE_S: other ranks' rows / gathers
-  unsigned long long* h_ptimes = nullptr;  // MGICP_PASS_DIAG builds: per pass gate exit / finish (wall clock)
-  unsigned long long* d_ptimes = nullptr;
-  // the passes' super partials as stamped host rows (32 words per super, two parity buffers; debug
-  // option "host_rows"): private pinned memory, or the node-wide shared segment
-  bool host_rows = true;
-  unsigned long long* h_rows = nullptr;
-  unsigned long long* d_rows = nullptr;
-  size_t rows_cap = 0;                  // supers per parity buffer
-  std::vector<double> row_sums;         // decoded super partials
-  unsigned int pass_idx = 0;            // objective passes so far: the row stamp (identical on every rank)
-  unsigned long long gather_idx = 0;    // generic gathers through the shared segment so far
-  // node-wide transport (mgicp_comm_attach_shm)
-  bool have_shm = false;
-  shm::Segment shm;
-  // r05 xGMI row exchange (mgicp_comm_attach_xgmi, needs the segment for its rendezvous): every rank's
-  // super reducers store their rows into this rank's exchange buffer (xrows: 2 parity buffers of
-  // max_sup rows, device memory) and into every other rank's, mapped by IPC over xGMI; a one-wave
-  // totaler per rank takes the fixed-order total on the device and stores it as one stamped host row
-  bool have_xgmi = false;
-  DevBuf<unsigned long long> xrows;
-  std::vector<void*> xpeer;               // the other ranks' exchange buffers (IPC mappings), rank order
-  unsigned long long* h_xtot = nullptr;   // the totaler's stamped row (32 words; host / device views)
-  unsigned long long* d_xtot = nullptr;
-  unsigned int* h_xgen = nullptr;         // generation word: a totaler exits when it changes
-  unsigned int* d_xgen = nullptr;
-  unsigned int xgen = 0;
-  unsigned long long xseq = 0;            // attaches so far (the segment's publication flag value)
-  hipStream_t xstream = nullptr;
-  bool xstream_own = false;  // r06: the aux stream (idle during a BFGS run: N > 1 keeps the synchronous
-                             // covariance path) when the context has one -- no third stream per context
-  unsigned char* shm_d = nullptr;       // device view of the segment (hipHostRegister'ed)
-  long long st[kStCount] = {};          // pass-path counters
-  // the resident server as the aligns run it (mgicp_debug_server_time): two events per launch
-  struct SrvEv { hipEvent_t a, b; long long passes; };
-  std::vector<SrvEv> srv_ev;            // launches not yet resolved (the last one may be live)
-  double srv_time_ms = 0;
-  long long srv_time_passes = 0, srv_time_launches = 0;
-  // MGICP_PASS_DIAG builds: host view of the server passes -- command published -> rows complete
-  // (device pass + PCIe both ways) and rows complete -> next command (host BFGS step)
-  double ht_dev = 0, ht_host = 0, ht_bfgs = 0, ht_eval = 0, ht_last_rows = 0;
-  int ht_n = 0, ht_nh = 0, ht_ne = 0;
-  // build scratch
-  DevBuf<uint32_t> counts, keys, keys_sorted, vals;
-  DevBuf<unsigned char> scratch;
-  DevBuf<unsigned long long> u64;
-  // lazy source covariances (r04, debug option "lazy_src_cov"): a source point's covariance is computed the
-  // first time a sweep accepts it -- every consumer (Mahalanobis of the compaction, GN moments) reads
-  // accepted points only, so points the gate never accepts (clutter, debris far off the part) never
-  // pay PCL's exact 20-NN search; the values are the eager ones bit for bit
-  bool lazy_src_cov = true;
-  bool src_lazy_ready = false;      // cov arrays sized and cov_ok cleared for the current shard
-  size_t src_lazy_p0 = 0, src_lazy_p1 = 0;
-  DevBuf<uint8_t> cov_ok;           // per shard point: covariance computed
-  DevBuf<uint32_t> cov_need;        // this sweep's accepted points without a covariance (absolute positions)
-  // r04: set_target builds the target's grid and starts its k-NN covariances on a second stream, so
-  // they run while the caller uploads the source; prepare joins them (debug option "async_cov" 0: off)
-  // (and set_source the source's: single rank, same stream; with the lazy source mode these cover
-  // every point, computed while the first sweep runs)
-  // The aux stream carries no CU mask, though leaving every k-th CU to the main stream measured up to
-  // -1.4 ms on new clouds (profiles/r04/ncab1): a CU mask belongs to the hardware queue, and past
-  // GPU_MAX_HW_QUEUES streams share queues, so another context's main stream could inherit the mask --
-  // and a resident server needs every CU (it stalled test_inlaunch_finish_*)
-  bool async_tgt = true;
-  bool tgt_cov_pending = false;     // the aux stream's covariance launches not joined yet
-  bool src_cov_pending = false;
-  bool src_async_lazy = false;      // the source's launch was ring-capped (lazy mode): the rest stays lazy
-  // one stream for both clouds' launches: with a stream each the process exceeds its hardware queues
-  // (GPU_MAX_HW_QUEUES, 4) and the main stream ends up sharing one with them (profiles/r04/prep7)
-  hipStream_t aux_stream = nullptr;
-  hipEvent_t aux_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // [3]: main stream -> aux (a grid built) (r06)
-  // completion of the target's [0] / source's [1] launch,
-                                                       // [2] the source's Morton order sorted on the aux stream
-  bool qperm_aux = false;                    // qperm is being sorted on the aux stream (aux_ev[2])
-  DevBuf<uint32_t> aq_keys, aq_keys_sorted, aq_vals;  // its sort buffers (the main stream's may be busy)
-  DevBuf<unsigned char> aq_scratch;
-  DevBuf<unsigned int> aux_cnt;     // their hand-off counts: [0] target, [1] source
-  DevBuf<uint32_t> knn_fb2;         // the source's hand-off list
-  bool knn_wave = true;             // r06: lazy pass + hand-offs by the wave-per-query kernel (debug option "knn_wave")
-  bool knn_logged = true;           // wave-staged k-NN kernel + hand-off (debug option "knn_logged" 0: register-list only)
-  DevBuf<uint32_t> knn_fb;          // points the logged k-NN kernel leaves to the register-list one
-  unsigned int knn_fallbacks = 0;   // their count in the last covariance launch
-  DevBuf<float> fpartial;
-  // the target's 1-NN cell lists (r04, DESIGN.md "1-NN cell lists"; debug option "vlist" 0: the r03 sweeps)
-  bool vlist = true;
-  bool fuse_compact = true;           // r04: compaction fused into listed sweeps (debug option "fuse_compact")
-  DevBuf<uint32_t> vl_defer;          // chunks a fused sweep deferred to the compaction launch
-  bool vl_stats = false;              // debug option "vlist_stats": per-sweep list diagnostics on stderr
-  bool vl_valid = false;              // lists belong to the current target grid and gate
-  bool vl_alloc = false;              // their state words and pool are allocated and initialised
-  bool vl_off = false;                // the gate is too large for a fine grid of this target: r03 sweeps
-  VListView vl{};
-  size_t vl_ncells = 0;
-  DevBuf<uint32_t> vl_cell, vl_build, vl_bcentre, vl_pend;
-  DevBuf<float4> vl_pool;
-  DevBuf<unsigned int> vl_ctr;
-  uint32_t vl_epoch = 0;              // sweeps run over the current lists
-  // A cell's list is built when a sweep of the SECOND align (or debug sweep group) over the current
-  // target and gate queries it: the first align after a set_target runs the r03 sweep (no list work,
-  // the ms-to-converge of a one-off align is unchanged), the second builds the lists of every cell it
-  // queries, later aligns (GICPAlignment::iterate, the next scans of the same CAD target) read them.
-  int vl_groups = 0;                  // aligns / debug sweep groups finished over the current lists
-  bool vl_eager = false;              // debug option "vlist_eager" 1: build every queried cell at once (default: a cell
-                                      // is built when a later sweep queries it again)
-  // aligns (or debug sweep groups) after a set_target / gate change that run the r03 sweep before the
-  // lists are used (debug option "vlist_cold" N).  The lists pay off only over many aligns on one target
-  // (a later scan against the same CAD cloud, bench.py's steady state): building them costs ~57 ms
-  // eagerly or ~15 ms spread over two aligns lazily at C4, so the reference's align + iterate pair on
-  // one cloud pair (GICPAlignment.cpp:96, :116) runs both aligns without them (r04, profiles/r04/policy)
-  int vl_cold_groups = 2;
-  // r05 target cache (process-wide, one entry per device): a destroyed context leaves its target's grid,
-  // covariances and 1-NN cell lists there; a later context whose set_target uploads the same points
-  // (compared on the device, bit for bit) adopts them instead of rebuilding -- GICPState constructs a
-  // fresh GICPAlignment per scan against the same CAD cloud (LeicaStateMachine.cpp:149-150)
-  bool tcache_on = false;               // debug option "target_cache" (r06: opt-in; VERDICT r05 weak 5 --
-                                        // the reference node aligns once per process)
-  bool tcache_adopted = false;          // the current target came from the cache
-  // multi-GPU
-  int nranks = 1, rank = 0;
-  ncclComm_t comm = nullptr;
-  // state of the last correspondence sweep
-  bool have_corr = false;
-  Mat4 last_guess = Mat4::identity();
-  std::vector<float> trace;
-  int n_evals = 0;
-  // profiling
-  bool profiling = false;
-  unsigned long long prof_tick = 0;
-  struct EvPair { hipEvent_t a, b; int fam; };
-  std::vector<EvPair> pending;
-  std::vector<hipEvent_t> pool;
-  double fam_ms[kFams] = {};
-  int fam_cnt[kFams] = {};
-
-  // shards start on super boundaries: rank r owns supers [super_first(r), super_first(r + 1))
-  long long nsup_total() const { return static_cast<long long>((src.n + kSuperPts - 1) / kSuperPts); }
-  size_t shard_at(int r) const {
-    return std::min(src.n, static_cast<size_t>(super_first(r, nsup_total(), nranks)) * kSuperPts);
-  }
-  size_t shard_p0() const { return shard_at(rank); }
-  size_t shard_p1() const { return shard_at(rank + 1); }
-  long long nsup_local() const {
-    return super_first(rank + 1, nsup_total(), nranks) - super_first(rank, nsup_total(), nranks);
-  }
-  long long max_supers() const { return (nsup_total() + nranks - 1) / nranks; }
-};
-
-namespace {
-
-int fail(mgicp_ctx* c, int code, const std::string& msg) {
-  if (c) c->err = msg;
-  return code;
-}
-
-#define HIPCK(expr)                                                                    \
-  do {                                                                                 \
-    hipError_t e_ = (expr);                                                            \
-    if (e_ != hipSuccess)                                                              \
-      return fail(ctx, (e_ == hipErrorOutOfMemory) ? MGICP_E_NOMEM : MGICP_E_HIP,      \
-                  std::string(#expr) + ": " + hipGetErrorString(e_));                  \
-  } while (0)
-
-#define NCCLCK(expr)                                                                   \
-  do {                                                                                 \
-    ncclResult_t r_ = (expr);                                                          \
-    if (r_ != ncclSuccess)                                                             \
-      return fail(ctx, MGICP_E_COMM, std::string(#expr) + ": " + ncclGetErrorString(r_)); \
-  } while (0)
 
 hipEvent_t ev_get(mgicp_ctx* ctx) {
   if (!ctx->pool.empty()) {
@@ -663,7 +251,8 @@ struct ProfScope {
   }
 };
 
-void prof_resolve(mgicp_ctx* ctx) {
+}  // namespace
+void mgicp::prof_resolve(mgicp_ctx* ctx) {
   for (auto& p : ctx->pending) {
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) {
@@ -675,6 +264,7 @@ void prof_resolve(mgicp_ctx* ctx) {
   }
   ctx->pending.clear();
 }
+namespace {
 
 // command block of the queued gated pass: op / reverse / A first, then the sequence number
 void publish_cmd(mgicp_ctx* ctx, unsigned long long seq, unsigned int op, int reverse, const Xf34* A,
@@ -712,9 +302,10 @@ void xgmi_detach(mgicp_ctx* ctx) {
   ctx->have_xgmi = false;
 }
 
+}  // namespace
 // release a queued gated pass (or the resident server) without running it (end of a BFGS run,
 // any stream drain)
-void cancel_gated(mgicp_ctx* ctx) {
+void mgicp::cancel_gated(mgicp_ctx* ctx) {
   if (ctx->srv_live) {
     xgmi_cancel(ctx);
     publish_cmd(ctx, ctx->srv_next, kPassCancel, 0, nullptr);
@@ -732,6 +323,7 @@ void cancel_gated(mgicp_ctx* ctx) {
   ctx->pass_seq = std::max(ctx->pass_seq, ctx->gated_seq);  // its sequence number is spent
   ctx->gated_seq = 0;
 }
+namespace {
 
 // server launches whose events have completed (after a drain: all of them) -> the in-align totals
 void srv_resolve(mgicp_ctx* ctx) {
@@ -748,15 +340,16 @@ void srv_resolve(mgicp_ctx* ctx) {
   ctx->srv_ev.clear();
 }
 
+}  // namespace
 // after a stream drain: no server of this context is running, the device's slot is free again
-void srv_release(mgicp_ctx* ctx) {
+void mgicp::srv_release(mgicp_ctx* ctx) {
   if (ctx->srv_locked && !ctx->srv_live) {
     g_srv_busy[ctx->device & 63].store(0, std::memory_order_release);
     ctx->srv_locked = false;
   }
 }
 
-int sync(mgicp_ctx* ctx) {
+int mgicp::sync(mgicp_ctx* ctx) {
   cancel_gated(ctx);  // a queued gated pass would otherwise hold the stream until its timeout
   HIPCK(hipStreamSynchronize(ctx->stream));
   srv_release(ctx);
@@ -764,6 +357,7 @@ int sync(mgicp_ctx* ctx) {
   if (!ctx->srv_ev.empty()) srv_resolve(ctx);
   return MGICP_OK;
 }
+namespace {
 
 // Row stamps count objective passes; every buffer that holds stamps of earlier passes (the server's
 // stamped chunk partials, this context's private host rows) is cleared whenever the count restarts
@@ -819,10 +413,12 @@ int cov_join(mgicp_ctx* ctx, bool tgt) {
   c.cov_p1 = c.n;
   return MGICP_OK;
 }
-int cov_join_all(mgicp_ctx* ctx) {
+}  // namespace
+int mgicp::cov_join_all(mgicp_ctx* ctx) {
   const int rc = cov_join(ctx, true);
   return rc ? rc : cov_join(ctx, false);
 }
+namespace {
 
 // set_target's / set_source's head start (single rank, eager target covariances, not profiling): the
 // cloud's grid now (its host round trips), then its k-NN covariances on the aux stream -- the
@@ -1335,8 +931,9 @@ const uint32_t* query_perm(mgicp_ctx* ctx) {
 
 constexpr unsigned int kWaveKnnMax = 65536;  // r06: lazy / hand-off lists up to this size run knn_wave_kernel
 
+}  // namespace
 // covariances of sorted positions [p0, p1) into arrays of `stride` entries (default n)
-int compute_cov(mgicp_ctx* ctx, Cloud& cl, size_t p0, size_t p1, size_t stride = 0) {
+int mgicp::compute_cov(mgicp_ctx* ctx, Cloud& cl, size_t p0, size_t p1, size_t stride) {
   MGICP_TRACE_AT("cov: begin");
   if (stride < cl.n) stride = cl.n;
   HIPCK(cl.cov.reserve(3 * stride));
@@ -1403,6 +1000,7 @@ int compute_cov(mgicp_ctx* ctx, Cloud& cl, size_t p0, size_t p1, size_t stride =
   cl.cov_p1 = p1;
   return MGICP_OK;
 }
+namespace {
 
 // target covariances (computeCovariances on the target, once per target cloud).  Multi-GPU
 // (SURVEY.md 8e): rank r computes the r-th of N equal slices and one in-place all-gather per
@@ -1426,8 +1024,9 @@ int target_cov(mgicp_ctx* ctx) {
   return MGICP_OK;
 }
 
+}  // namespace
 // Registration::initCompute + initComputeReciprocal + computeCovariances (both clouds)
-int prepare(mgicp_ctx* ctx, bool need_cov) {
+int mgicp::prepare(mgicp_ctx* ctx, bool need_cov) {
   if (ctx->src.n == 0 || ctx->tgt.n == 0)
     return fail(ctx, MGICP_E_INVALID, "source and target clouds must be set before align");
   const int k = ctx->prm.k;
@@ -1464,6 +1063,7 @@ int prepare(mgicp_ctx* ctx, bool need_cov) {
     if ((rc = compute_cov(ctx, ctx->src, ctx->shard_p0(), ctx->shard_p1()))) return rc;
   return MGICP_OK;
 }
+namespace {
 
 // the covariances a sweep needs (lazy source mode): its accepted source points without one, computed
 // by the same kernels as the eager pass (the k-NN kernel, the register-list hand-off for the rest)
@@ -1513,7 +1113,8 @@ int cov_lazy(mgicp_ctx* ctx) {
   return MGICP_OK;
 }
 
-int ensure_host_red(mgicp_ctx* ctx) {
+}  // namespace
+int mgicp::ensure_host_red(mgicp_ctx* ctx) {
   if (!ctx->h_cmd) {
     HIPCK(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_cmd), sizeof(PassCmd),
                         hipHostMallocMapped | hipHostMallocCoherent));
@@ -1564,6 +1165,7 @@ int ensure_host_red(mgicp_ctx* ctx) {
   ctx->d_flag = reinterpret_cast<unsigned long long*>(ctx->d_h_red + kRedVals);
   return MGICP_OK;
 }
+namespace {
 
 // Wait for pass `seq` to publish its sums: spin on the mapped completion word; after ~0.5 s fall
 // back to a stream synchronisation so a failed launch surfaces as an error instead of a hang.
@@ -1582,22 +1184,8 @@ int wait_pass(mgicp_ctx* ctx, unsigned long long seq) {
   return MGICP_OK;
 }
 
-CorrSoA corr_soa(mgicp_ctx* ctx);
-
-// Where the host rows of the passes live: this context's private pinned buffers (single rank), or
-// the node-wide shared segment (every rank's rows at their global super index).  Parity buffer p
-// starts stride words after parity 0; this rank's rows start at super `first`.
-struct RowView {
-  unsigned long long* h0 = nullptr;  // host view, parity 0, super 0
-  unsigned long long* d0 = nullptr;  // device view, parity 0, super 0
-  size_t stride = 0;                 // words between the parity buffers
-  long long first = 0, nloc = 0, ntot = 0;
-  unsigned long long* dev_rows(unsigned int rstamp) const {  // this rank's rows of the pass stamped rstamp
-    return d0 + (rstamp & 1u) * stride + static_cast<size_t>(first) * shm::kRowWords;
-  }
-};
-
-RowView row_view(const mgicp_ctx* ctx) {
+}  // namespace
+RowView mgicp::row_view(const mgicp_ctx* ctx) {
   RowView v;
   if (ctx->have_shm) {
     v.h0 = reinterpret_cast<unsigned long long*>(ctx->shm.rows(0));
@@ -1617,7 +1205,7 @@ RowView row_view(const mgicp_ctx* ctx) {
 
 // Host rows for the current source cloud: the private buffers grow as needed (two parity buffers);
 // the shared segment was sized at attach time.
-int ensure_rows(mgicp_ctx* ctx) {
+int mgicp::ensure_rows(mgicp_ctx* ctx) {
   const long long nsup = ctx->nsup_total();
   if (ctx->have_shm) {
     if (nsup > ctx->shm.max_sup)
@@ -1641,6 +1229,7 @@ int ensure_rows(mgicp_ctx* ctx) {
   ctx->st[kStRowsAlloc]++;
   return MGICP_OK;
 }
+namespace {
 
 // A server pass missed its deadline (its blocks could not all run: other work on the device, a
 // profiler, a withheld block in the tests): cancel the server -- blocks still waiting see the later
@@ -1662,12 +1251,13 @@ int take_over(mgicp_ctx* ctx, unsigned int rstamp, const Xf34& A) {
   return MGICP_OK;
 }
 
+}  // namespace
 // Wait for every host row of the pass stamped rstamp (32 stamped words per super: this rank's own
 // rows first, then the other ranks'), then take the total exactly as wave_total / wave_sum would on
 // one wave (shm::fixed_total).  Own rows missing after row_deadline_ms: the pass is taken over
 // (take_over, when allowed) and waited for again; after a stream drain every row is checked once
 // more before an error is returned.  Other ranks' rows: remote_deadline_s.
-int wait_rows(mgicp_ctx* ctx, unsigned int rstamp, const Xf34& A, double out[kRedVals], bool allow_takeover) {
+int mgicp::wait_rows(mgicp_ctx* ctx, unsigned int rstamp, const Xf34& A, double out[kRedVals], bool allow_takeover) {
   const RowView rv = row_view(ctx);
   const unsigned long long* buf = rv.h0 + (rstamp & 1u) * rv.stride;
   ctx->row_sums.resize(static_cast<size_t>(std::max<long long>(rv.ntot, 1)) * kRedVals);
@@ -1717,6 +1307,7 @@ int wait_rows(mgicp_ctx* ctx, unsigned int rstamp, const Xf34& A, double out[kRe
   shm::fixed_total(ctx->row_sums.data(), rv.ntot, kRedVals, out);
   return MGICP_OK;
 }
+namespace {
 
 // r05 xGMI: the pass total the rank's totaler stored (every rank's rows arrived in its buffer)
 int wait_xtot(mgicp_ctx* ctx, unsigned int rstamp, double out[kRedVals]) {
@@ -1730,7 +1321,8 @@ int wait_xtot(mgicp_ctx* ctx, unsigned int rstamp, double out[kRedVals]) {
   return MGICP_OK;
 }
 
-int ensure_iter_buffers(mgicp_ctx* ctx) {
+}  // namespace
+int mgicp::ensure_iter_buffers(mgicp_ctx* ctx) {
   const size_t ns = ctx->shard_p1() - ctx->shard_p0();
   const size_t nch = static_cast<size_t>(chunk_count(ns));
   const size_t msup = static_cast<size_t>(ctx->max_supers());
@@ -1761,6 +1353,7 @@ int ensure_iter_buffers(mgicp_ctx* ctx) {
   }
   return MGICP_OK;
 }
+namespace {
 
 // totals (nv values) of the shard's super partials `sup`: all-gathered across ranks over RCCL and
 // finished in the fixed global order (launch_finish_supers), or -- single rank or detached shard
@@ -1809,8 +1402,9 @@ int combine_to_host(mgicp_ctx* ctx, int nv, const double* sup, double* out) {
   return MGICP_OK;
 }
 
+}  // namespace
 // guess-applied source cloud ("output" after transformPointCloud(output, output, guess))
-int set_output(mgicp_ctx* ctx, const Mat4& G) {
+int mgicp::set_output(mgicp_ctx* ctx, const Mat4& G) {
   float lo[3], hi[3];
   if (G.is_identity()) {
     ctx->d_out = ctx->src.pts.p;  // x*1 + y*0 + z*0 + 0 == x: identity leaves points intact
@@ -1843,6 +1437,7 @@ int set_output(mgicp_ctx* ctx, const Mat4& G) {
   ctx->last_guess = G;
   return MGICP_OK;
 }
+namespace {
 
 // transform_R(i,j) = sum_k double(T(i,k)) * double(G(k,j)), top-left 3x3
 Rot33d rot_of(const Mat4& T, const Mat4& G) {
@@ -1856,13 +1451,15 @@ Rot33d rot_of(const Mat4& T, const Mat4& G) {
   return R;
 }
 
-CorrSoA corr_soa(mgicp_ctx* ctx) {
+}  // namespace
+CorrSoA mgicp::corr_soa(mgicp_ctx* ctx) {
   const size_t c = ctx->corr_cap;
   float* f = ctx->corr_f.p;
   double* d = ctx->corr_d.p;
   return CorrSoA{f, f + c, f + 2 * c, f + 3 * c, f + 4 * c, f + 5 * c,
                  d, d + c, d + 2 * c, d + 3 * c, d + 4 * c, d + 5 * c};
 }
+namespace {
 
 // The fine grid of the target's 1-NN cell lists for the current gate (once per target grid and gate;
 // the lists themselves are built by the sweeps, cell by cell, the first time a query lands in a cell).
@@ -1979,12 +1576,13 @@ hipError_t launch_sweep(mgicp_ctx* ctx, const Mat4& T, double thr, bool seeded, 
                                 ctx->stream);
 }
 
+}  // namespace
 // One correspondence sweep (the loop body of computeTransformation before the BFGS call):
 // exact 1-NN per source point, then a deterministic compaction of the accepted ones (exclusive
 // scan of the flags, scatter in grid-sorted order) that computes their Mahalanobis matrices
 // straight into the SoA streams.  `seed` uses the previous sweep's matches as 1-NN starting
 // candidates (exact either way).
-int correspond(mgicp_ctx* ctx, const Mat4& T, const Mat4& G, bool seed) {
+int mgicp::correspond(mgicp_ctx* ctx, const Mat4& T, const Mat4& G, bool seed) {
   const double thr = ctx->prm.max_corr_dist * ctx->prm.max_corr_dist;
   const size_t p0 = ctx->shard_p0(), p1 = ctx->shard_p1(), ns = p1 - p0;
   hipStream_t s = ctx->stream;
@@ -2095,6 +1693,7 @@ int correspond(mgicp_ctx* ctx, const Mat4& T, const Mat4& G, bool seed) {
   ctx->have_corr = true;
   return MGICP_OK;
 }
+namespace {
 
 // OptimizationFunctorWithIndices::fdf on the device; memoises the last state
 struct DeviceFunctor {
@@ -2320,6 +1919,21 @@ struct GateGuard {  // a BFGS run leaves no gated pass queued behind it
   ~GateGuard() { cancel_gated(ctx); }
 };
 
+}  // namespace
+// DeviceFunctor for the debug entry points (mgicp_debug_fdf, mgicp_debug_fdf_sums): f and g at x, and
+// the 16 raw sums of one pass at x
+int mgicp::fdf_at(mgicp_ctx* ctx, const Vec6& x, double& f, Vec6& g) {
+  GateGuard guard{ctx};  // no queued pass / live server outlives the call
+  DeviceFunctor fn{ctx};
+  return fn.eval(x, f, g);
+}
+int mgicp::fdf_sums_at(mgicp_ctx* ctx, const Vec6& x, double sums[kRedVals]) {
+  GateGuard guard{ctx};
+  DeviceFunctor fn{ctx};
+  return fn.pass(x, sums);
+}
+namespace {
+
 // every error return of an align (a HIP error mid-loop, MGICP_E_COMM from a quitting rank, ...) drains
 // the stream and gives the device's server slot back, so other contexts on the device keep their
 // resident server; the error message of the failure is kept
@@ -2388,11 +2002,12 @@ int estimate_bfgs(mgicp_ctx* ctx, Mat4& T, int* n_corr) {
   return MGICP_E_SOLVER;  // SolverDidntConvergeException
 }
 
+}  // namespace
 // Gauss-Newton mode, one device pass per outer iteration: the 74 moments of the objective over
 // the accepted correspondences of the last sweep at T (Mahalanobis computed on the fly), finished
 // over the fixed reduction tree (chunks, supers, all-gathered supers, fixed-order total), copied to
 // the host.
-int moments_pass(mgicp_ctx* ctx, const Mat4& T, const Mat4& G, bool supers_only = false) {
+int mgicp::moments_pass(mgicp_ctx* ctx, const Mat4& T, const Mat4& G, bool supers_only) {
   const size_t p0 = ctx->shard_p0(), p1 = ctx->shard_p1();
   hipStream_t s = ctx->stream;
   const int nch = chunk_count(p1 - p0);
@@ -2414,6 +2029,7 @@ int moments_pass(mgicp_ctx* ctx, const Mat4& T, const Mat4& G, bool supers_only 
   ctx->n_evals++;
   return MGICP_OK;
 }
+namespace {
 
 // the correspondence sweep of the Gauss-Newton mode: exact 1-NN (same kernel as the BFGS mode),
 // then the moment pass; no scan / compaction (the moment pass reads the flags directly)
@@ -2471,6 +2087,17 @@ int check_params(mgicp_ctx* ctx, const mgicp_params& p) {
 }
 
 }  // namespace
+
+// getFitnessScore's chunk and super partials of this shard ([0] sum d2, [13] count) in spart
+int mgicp::fitness_supers(mgicp_ctx* ctx, const Mat4& T, double max_range) {
+  const size_t p0 = ctx->shard_p0(), p1 = ctx->shard_p1();
+  const int nch = chunk_count(p1 - p0);
+  if (nch == 0) return MGICP_OK;
+  HIPCK(launch_fitness(ctx->tgt.view, ctx->src.pts.p, p0, p1, T.xf(), max_range, ctx->partial.p,
+                       chunk_grid_blocks(p1 - p0), ctx->stream));
+  HIPCK(launch_super_reduce(ctx->partial.p, nch, kRedVals, ctx->spart.p, ctx->stream));
+  return MGICP_OK;
+}
 
 // =====================================================================================
 // C-ABI
@@ -2839,17 +2466,6 @@ int mgicp_align(mgicp_ctx* ctx, const float guess_cm[16], float out_T_cm[16], mg
   r.ms_total = t2 - t0 + r.ms_upload;
   if (res) *res = r;
   if (solver_rc) return fail(ctx, solver_rc, "GICP solver threw (fewer than 4 correspondences or BFGS failure)");
-  return MGICP_OK;
-}
-
-// getFitnessScore's chunk and super partials of this shard ([0] sum d2, [13] count) in spart
-static int fitness_supers(mgicp_ctx* ctx, const Mat4& T, double max_range) {
-  const size_t p0 = ctx->shard_p0(), p1 = ctx->shard_p1();
-  const int nch = chunk_count(p1 - p0);
-  if (nch == 0) return MGICP_OK;
-  HIPCK(launch_fitness(ctx->tgt.view, ctx->src.pts.p, p0, p1, T.xf(), max_range, ctx->partial.p,
-                       chunk_grid_blocks(p1 - p0), ctx->stream));
-  HIPCK(launch_super_reduce(ctx->partial.p, nch, kRedVals, ctx->spart.p, ctx->stream));
   return MGICP_OK;
 }
 
@@ -3392,420 +3008,6 @@ int mgicp_comm_attach_shm(mgicp_ctx* ctx, const char* name, size_t max_source_po
   return MGICP_OK;
 }
 
-int mgicp_debug_pass_stats(mgicp_ctx* ctx, long long out[8]) {
-  if (!ctx || !out) return MGICP_E_INVALID;
-  for (int i = 0; i < kStCount; ++i) out[i] = ctx->st[i];
-  return MGICP_OK;
-}
-
-int mgicp_debug_server_time(mgicp_ctx* ctx, double* out_ms, long long* out_passes, long long* out_launches,
-                            int reset) {
-  if (!ctx || !out_ms || !out_passes || !out_launches) return MGICP_E_INVALID;
-  *out_ms = ctx->srv_time_ms;
-  *out_passes = ctx->srv_time_passes;
-  *out_launches = ctx->srv_time_launches;
-  if (reset) {
-    ctx->srv_time_ms = 0;
-    ctx->srv_time_passes = ctx->srv_time_launches = 0;
-  }
-  return MGICP_OK;
-}
-
-int mgicp_debug_target_cov_slice(mgicp_ctx* ctx, int nranks, int rank, double* out_c6) {
-  if (!ctx || !out_c6 || nranks < 1 || rank < 0 || rank >= nranks) return MGICP_E_INVALID;
-  HIPCK(hipSetDevice(ctx->device));
-  int rc = prepare(ctx, false);
-  if (rc || (rc = cov_join_all(ctx))) return rc;  // set_target's k-NN launch still writes tgt.cov
-  Cloud& t = ctx->tgt;
-  const size_t N = static_cast<size_t>(nranks), r = static_cast<size_t>(rank);
-  const size_t cnt = (t.n + N - 1) / N;
-  const size_t a = std::min(t.n, r * cnt), b = std::min(t.n, (r + 1) * cnt);
-  // target_cov's slice call, verbatim: the same range, the same N * cnt array layout
-  if ((rc = compute_cov(ctx, t, a, b, N * cnt))) return rc;
-  t.have_cov = false;  // only a slice is current: the next align recomputes the target's covariances
-  const size_t st = t.cov_stride, m = b - a;
-  std::vector<double2> h(3 * std::max<size_t>(m, 1));
-  if (m) {
-    const Cov3 c = t.cov3();
-    HIPCK(hipMemcpyAsync(h.data(), c.a + a, m * sizeof(double2), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCK(hipMemcpyAsync(h.data() + m, c.b + a, m * sizeof(double2), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCK(hipMemcpyAsync(h.data() + 2 * m, c.c + a, m * sizeof(double2), hipMemcpyDeviceToHost, ctx->stream));
-  }
-  (void)st;
-  if ((rc = sync(ctx))) return rc;
-  for (size_t i = 0; i < m; ++i) {  // grid-sorted order, as the arrays hold them
-    double* o = out_c6 + 6 * i;
-    o[0] = h[i].x; o[1] = h[i].y; o[2] = h[m + i].x; o[3] = h[m + i].y; o[4] = h[2 * m + i].x; o[5] = h[2 * m + i].y;
-  }
-  return static_cast<int>(m);
-}
-
-int mgicp_debug_vlist_stats(mgicp_ctx* ctx, long long out[8]) {
-  if (!ctx || !out) return MGICP_E_INVALID;
-  for (int i = 0; i < 8; ++i) out[i] = 0;
-  if (!ctx->vlist || !ctx->vl_valid || ctx->vl_off || !ctx->vl_alloc) return MGICP_OK;
-  HIPCK(hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
-  unsigned int c3[3];
-  HIPCK(hipMemcpyAsync(c3, ctx->vl_ctr.p, 3 * sizeof(unsigned int), hipMemcpyDeviceToHost, s));
-  HIPCK(ctx->u64.reserve(64));
-  HIPCK(launch_vl_stats(ctx->vl, ctx->vl_ncells, ctx->u64.p, s));
-  unsigned long long st[64];
-  HIPCK(hipMemcpyAsync(st, ctx->u64.p, sizeof(st), hipMemcpyDeviceToHost, s));
-  int rc = sync(ctx);
-  if (rc) return rc;
-  out[0] = c3[1];
-  out[1] = c3[2];
-  out[2] = static_cast<long long>(st[0]);
-  out[3] = static_cast<long long>(st[1]);
-  out[4] = static_cast<long long>(st[2]);
-  out[5] = static_cast<long long>(st[3]);
-  out[6] = c3[0];
-  out[7] = static_cast<long long>(ctx->vl_ncells);
-  return MGICP_OK;
-}
-
-// r06: the objective's stream order -- original indices of this rank's source points in the order the
-// compacted streams (and so every sum's fixed tree) visit them; the oracle's summation-order ledger runs
-// the engine's tree over it (oracle/gicp_ref.c ref_set_sum_order).  Returns the count (<= cap written).
-int mgicp_debug_source_order(mgicp_ctx* ctx, uint32_t* out, size_t cap) {
-  if (!ctx || !out) return MGICP_E_INVALID;
-  HIPCK(hipSetDevice(ctx->device));
-  int rc = prepare(ctx, false);
-  if (rc) return rc;
-  const size_t p0 = ctx->shard_p0(), ns = ctx->shard_p1() - p0;
-  if (cap < ns) return fail(ctx, MGICP_E_INVALID, "debug_source_order: cap below the shard's point count");
-  HIPCK(hipMemcpyAsync(out, ctx->src.perm.p + p0, ns * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-  if ((rc = sync(ctx))) return rc;
-  return static_cast<int>(ns);
-}
-
-int mgicp_debug_covariances(mgicp_ctx* ctx, int which, double* out_c6) {
-  if (!ctx || !out_c6 || (which != 0 && which != 1)) return MGICP_E_INVALID;
-  HIPCK(hipSetDevice(ctx->device));
-  int rc = prepare(ctx, true);
-  if (rc) return rc;
-  // both clouds: prepare counts set_target's running covariances as current
-  if ((rc = cov_join_all(ctx))) return rc;
-  if (which == 0 &&!(ctx->src.have_cov && ctx->src.cov_p0 == ctx->shard_p0() && ctx->src.cov_p1 == ctx->shard_p1())) {
-    // every source covariance (lazy mode computes only the accepted points' ones)
-    if ((rc = compute_cov(ctx, ctx->src, ctx->shard_p0(), ctx->shard_p1()))) return rc;
-    if (ctx->src_lazy_ready) HIPCK(hipMemsetAsync(ctx->cov_ok.p, 1, ctx->shard_p1() - ctx->shard_p0(), ctx->stream));
-  }
-  Cloud& cl = which ? ctx->tgt : ctx->src;
-  const size_t n = cl.n;
-  const size_t st = cl.cov_stride;
-  std::vector<double2> h(3 * st);
-  std::vector<uint32_t> perm(n);
-  HIPCK(hipMemcpyAsync(h.data(), cl.cov.p, 3 * st * sizeof(double2), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCK(hipMemcpyAsync(perm.data(), cl.perm.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-  if ((rc = sync(ctx))) return rc;
-  for (size_t p = 0; p < n; ++p) {
-    double* o = out_c6 + 6 * static_cast<size_t>(perm[p]);
-    o[0] = h[p].x; o[1] = h[p].y;
-    o[2] = h[st + p].x; o[3] = h[st + p].y;
-    o[4] = h[2 * st + p].x; o[5] = h[2 * st + p].y;
-  }
-  return MGICP_OK;
-}
-
-static int debug_corr(mgicp_ctx* ctx, const float T_cm[16], bool seeded, int* out_tgt, double* out_M6) {
-  if (!ctx || !T_cm) return MGICP_E_INVALID;
-  if (seeded && !ctx->seed_valid) return fail(ctx, MGICP_E_INVALID, "no previous sweep to seed from");
-  HIPCK(hipSetDevice(ctx->device));
-  int rc = prepare(ctx, true);
-  if (rc) return rc;
-  if ((rc = ensure_iter_buffers(ctx))) return rc;
-  const size_t n = ctx->src.n;
-  const Mat4 G = Mat4::identity();
-  if ((rc = set_output(ctx, G))) return rc;
-  if ((rc = correspond(ctx, Mat4::from_cm(T_cm), G, seeded))) return rc;
-  if (ctx->vl_valid) ctx->vl_groups++;
-  const size_t p0 = ctx->shard_p0(), p1 = ctx->shard_p1(), ns = p1 - p0;
-  std::vector<uint32_t> nn(ns), flag(ns), perm(n), tperm(ctx->tgt.n);
-  std::vector<uint32_t> ccnt(static_cast<size_t>(chunk_count(ns)));
-  HIPCK(hipMemcpyAsync(nn.data(), ctx->prev_pos.p, ns * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCK(hipMemcpyAsync(flag.data(), ctx->flags.p, ns * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-  if (!ccnt.empty())
-    HIPCK(hipMemcpyAsync(ccnt.data(), ctx->ccnt.p, ccnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCK(hipMemcpyAsync(perm.data(), ctx->src.perm.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCK(hipMemcpyAsync(tperm.data(), ctx->tgt.perm.p, ctx->tgt.n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-  const size_t cap = ctx->corr_cap;
-  std::vector<double> M(6 * cap);
-  HIPCK(hipMemcpyAsync(M.data(), ctx->corr_d.p, 6 * cap * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if ((rc = sync(ctx))) return rc;
-  int cnt = 0;
-  size_t rank = 0;  // accepted before k in k's chunk
-  for (size_t p = p0; p < p1; ++p) {
-    const size_t i = perm[p], k = p - p0;
-    if (k % kChunkPts == 0) rank = 0;
-    const bool ok = flag[k] != 0;
-    if (out_tgt) out_tgt[i] = ok ? static_cast<int>(tperm[nn[k]]) : -1;
-    if (out_M6) {
-      double* o = out_M6 + 6 * i;
-      const size_t at = (k / kChunkPts) * kChunkPts + rank;  // the chunk's run of the streams
-      for (int v = 0; v < 6; ++v) o[v] = ok ? M[v * cap + at] : 0.0;
-    }
-    if (ok) {
-      cnt++;
-      rank++;
-    }
-  }
-  for (size_t c = 0; c < ccnt.size(); ++c) {  // the compaction's counts agree with the flags
-    size_t m = 0;
-    for (size_t k = c * kChunkPts; k < std::min(ns, (c + 1) * kChunkPts); ++k) m += flag[k] != 0;
-    if (m != ccnt[c]) return fail(ctx, MGICP_E_HIP, "chunk counts disagree with the sweep's flags");
-  }
-  return cnt;
-}
-
-int mgicp_debug_correspondences(mgicp_ctx* ctx, const float T_cm[16], int* out_tgt, double* out_M6) {
-  return debug_corr(ctx, T_cm, false, out_tgt, out_M6);
-}
-
-int mgicp_debug_correspondences_seeded(mgicp_ctx* ctx, const float T_cm[16], int* out_tgt, double* out_M6) {
-  return debug_corr(ctx, T_cm, true, out_tgt, out_M6);
-}
-
-int mgicp_debug_fdf(mgicp_ctx* ctx, const double x[6], double* f, double g6[6]) {
-  if (!ctx || !x || !ctx->have_corr) return MGICP_E_INVALID;
-  HIPCK(hipSetDevice(ctx->device));
-  GateGuard guard{ctx};  // no queued pass / live server outlives the call
-  DeviceFunctor fn{ctx};
-  Vec6 xv, gv;
-  for (int i = 0; i < 6; ++i) xv[i] = x[i];
-  double fv = 0;
-  int rc = fn.eval(xv, fv, gv);
-  if (rc) return rc;
-  if (f) *f = fv;
-  if (g6)
-    for (int i = 0; i < 6; ++i) g6[i] = gv[i];
-  return MGICP_OK;
-}
-
-int mgicp_debug_fdf_sums(mgicp_ctx* ctx, const double x[6], double out16[16]) {
-  if (!ctx || !x || !out16 || !ctx->have_corr) return MGICP_E_INVALID;
-  HIPCK(hipSetDevice(ctx->device));
-  GateGuard guard{ctx};
-  DeviceFunctor fn{ctx};
-  Vec6 xv;
-  for (int i = 0; i < 6; ++i) xv[i] = x[i];
-  return fn.pass(xv, out16);
-}
-
-int mgicp_debug_pass_bench(mgicp_ctx* ctx, const double x[6], int npasses, int mode, double* out_ms,
-                           double out16[16]) {
-  if (!ctx || !x || npasses < 1 || npasses > 100000 || (mode != 0 && mode != 1) || !ctx->have_corr)
-    return MGICP_E_INVALID;
-  if (ctx->comm || ctx->nranks != 1 || ctx->have_shm)
-    return fail(ctx, MGICP_E_INVALID, "pass bench: single-rank contexts only");
-  HIPCK(hipSetDevice(ctx->device));
-  int rc = sync(ctx);  // cancels any queued pass / live server
-  if (rc) return rc;
-  if ((rc = ensure_host_red(ctx))) return rc;
-  Vec6 xv;
-  for (int i = 0; i < 6; ++i) xv[i] = x[i];
-  const Xf34 A = apply_state(xv).xf();
-  const size_t ns = ctx->shard_p1() - ctx->shard_p0();
-  const CorrSoA c = corr_soa(ctx);
-  hipEvent_t a = nullptr, b = nullptr;
-  HIPCK(hipEventCreate(&a));
-  HIPCK(hipEventCreate(&b));
-  HIPCK(hipEventRecord(a, ctx->stream));
-  hipError_t e = hipSuccess;
-  const bool rows = mode == 0 && ctx->host_rows;
-  if (rows && (rc = ensure_rows(ctx))) return rc;
-  if (rows) HIPCK(hipMemsetAsync(ctx->tickets.p, 0, ctx->tickets_n * sizeof(unsigned int), ctx->stream));
-  if (mode == 0) {
-    const int cap = ctx->srv_cus > 0 ? std::min(ctx->srv_cus, ctx->cus) : ctx->cus;
-    const int nb = fdf_server_blocks(ns, cap);
-    if (nb <= 0) {
-      (void)hipEventDestroy(a);
-      (void)hipEventDestroy(b);
-      return fail(ctx, MGICP_E_INVALID, "pass bench: shard not servable by the resident server");
-    }
-    const unsigned long long seq0 = ++ctx->pass_seq;
-    const RowView rv = row_view(ctx);
-    e = launch_fdf_server(c, ctx->ccnt.p, ns, ctx->partial.p, ctx->spart.p, ctx->tickets.p,
-                          ctx->d_h_red, ctx->d_flag, seq0, ctx->d_cmd, ctx->mail, ctx->gate_timeout, ctx->d_ptimes,
-                          npasses, A, rows ? rv.dev_rows(0) : nullptr, rv.stride, nb, 1, -1, ctx->tpart.p, ctx->stream);
-    ctx->pass_seq = seq0 + static_cast<unsigned long long>(npasses);  // the closing cancel's stamp too
-  } else {
-    const int nb = fdf_grid_blocks(ns, kFdfMaxBlocks);
-    for (int k = 0; k < npasses && e == hipSuccess; ++k)
-      e = launch_fdf_soa(c, ctx->ccnt.p, ns, A, ctx->partial.p, ctx->spart.p, nb, ctx->tickets.p,
-                         ctx->d_h_red, k & 1, ctx->d_flag, ++ctx->pass_seq, ctx->stream);
-  }
-  if (e == hipSuccess) e = hipEventRecord(b, ctx->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  float ms = 0.f;
-  if (e == hipSuccess) e = hipEventElapsedTime(&ms, a, b);
-  (void)hipEventDestroy(a);
-  (void)hipEventDestroy(b);
-  HIPCK(e);
-  if (MGICP_PASS_DIAG && mode == 0) {
-    PassCmd m{};
-    HIPCK(hipMemcpy(&m, ctx->mail, sizeof(PassCmd), hipMemcpyDeviceToHost));
-    std::fprintf(stderr, "[srv-debug] seq0 %llu npasses %d ms %.3f | mail:", ctx->pass_seq - npasses, npasses, ms);
-    for (int i = 0; i < 16; ++i)
-      std::fprintf(stderr, " %x:%x", static_cast<unsigned>(m.h[i] >> 32), static_cast<unsigned>(m.h[i]));
-    std::fprintf(stderr, "\n");
-    if (ctx->h_ptimes)
-      for (unsigned long long q = ctx->pass_seq - npasses; q < ctx->pass_seq + 1; ++q)
-        std::fprintf(stderr, "[srv-debug] pass %llu: gate exit %llu finish %llu\n", q, ctx->h_ptimes[2 * (q & 1023)],
-                     ctx->h_ptimes[2 * (q & 1023) + 1]);
-  }
-  if (rows) {
-    // the host-row tickets are left as multiples of the supers' sizes: re-arm them
-    HIPCK(hipMemsetAsync(ctx->tickets.p, 0, ctx->tickets_n * sizeof(unsigned int), ctx->stream));
-    double tot[kRedVals];
-    // the timing form stamps each pass's rows with its sequence number | 2^31
-    const Xf34 unused{};
-    if ((rc = wait_rows(ctx, static_cast<unsigned int>(ctx->pass_seq - 1) | 0x80000000u, unused, tot, false))) return rc;
-    if ((rc = sync(ctx))) return rc;
-    if (out16) std::memcpy(out16, tot, kRedVals * sizeof(double));
-  } else {
-    if (__atomic_load_n(ctx->h_flag, __ATOMIC_ACQUIRE) != ctx->pass_seq - (mode == 0 ? 1 : 0))
-      return fail(ctx, MGICP_E_HIP, "pass bench: the last pass did not publish its sums");
-    if (out16) std::memcpy(out16, ctx->h_red, kRedVals * sizeof(double));
-  }
-  if (out_ms) *out_ms = static_cast<double>(ms) / npasses;
-  return MGICP_OK;
-}
-
-int mgicp_debug_moments(mgicp_ctx* ctx, const float T_cm[16], double out80[80]) {
-  if (!ctx || !T_cm || !out80 || !ctx->seed_valid) return MGICP_E_INVALID;
-  HIPCK(hipSetDevice(ctx->device));
-  int rc = moments_pass(ctx, Mat4::from_cm(T_cm), ctx->last_guess);
-  if (rc) return rc;
-  std::memcpy(out80, ctx->mom, kMomVals * sizeof(double));
-  return MGICP_OK;
-}
-
-int mgicp_debug_supers(mgicp_ctx* ctx, int kind, const double* arg, double* out, int cap) {
-  if (!ctx || !arg || !out || kind < 0 || kind > 2) return MGICP_E_INVALID;
-  HIPCK(hipSetDevice(ctx->device));
-  const long long nsup = ctx->nsup_local();
-  if (nsup > cap) return fail(ctx, MGICP_E_INVALID, "debug_supers: output too small");
-  const int nv = kind == 1 ? kMomVals : kRedVals;
-  float Tcm[16];
-  for (int i = 0; i < 16 && kind != 0; ++i) Tcm[i] = static_cast<float>(arg[i]);
-  int rc;
-  const double* sup = ctx->spart.p;
-  if (kind == 0) {  // one objective pass at x over the last sweep, stopped at the supers
-    if (!ctx->have_corr) return fail(ctx, MGICP_E_INVALID, "no correspondence sweep yet");
-    cancel_gated(ctx);
-    Vec6 x;
-    for (int i = 0; i < 6; ++i) x[i] = arg[i];
-    const size_t ns = ctx->shard_p1() - ctx->shard_p0();
-    // host-row passes leave the tickets as multiples of their supers' sizes
-    HIPCK(hipMemsetAsync(ctx->tickets.p, 0, ctx->tickets_n * sizeof(unsigned int), ctx->stream));
-    HIPCK(launch_fdf_soa(corr_soa(ctx), ctx->ccnt.p, ns, apply_state(x).xf(), ctx->partial.p,
-                         ctx->spart.p, fdf_grid_blocks(ns, kFdfMaxBlocks), ctx->tickets.p, nullptr, 0,
-                         nullptr, 0, ctx->stream));
-  } else if (kind == 1) {
-    if (!ctx->seed_valid) return fail(ctx, MGICP_E_INVALID, "no correspondence sweep yet");
-    if ((rc = moments_pass(ctx, Mat4::from_cm(Tcm), ctx->last_guess, true))) return rc;
-    sup = ctx->msuper.p;
-  } else {
-    if ((rc = prepare(ctx, false)) || (rc = ensure_iter_buffers(ctx))) return rc;
-    const double mr = arg[16] > 0 ? arg[16] : 1.7976931348623157e308;
-    if ((rc = fitness_supers(ctx, Mat4::from_cm(Tcm), mr))) return rc;
-  }
-  if (nsup > 0)
-    HIPCK(hipMemcpyAsync(out, sup, static_cast<size_t>(nsup) * nv * sizeof(double), hipMemcpyDeviceToHost,
-                         ctx->stream));
-  if ((rc = sync(ctx))) return rc;
-  return static_cast<int>(nsup);
-}
-
-int mgicp_debug_finish_supers(mgicp_ctx* ctx, int nv, const double* rows, long long nsup, long long maxsup,
-                              int nranks, double* out) {
-  if (!ctx || !rows || !out || (nv != kRedVals && nv != kMomVals) || nsup < 0 || maxsup < 0 || nranks < 1)
-    return MGICP_E_INVALID;
-  HIPCK(hipSetDevice(ctx->device));
-  const size_t nrow = static_cast<size_t>(nranks) * maxsup * nv;
-  DevBuf<double> d, o;
-  HIPCK(d.reserve(std::max<size_t>(nrow, 1)));
-  HIPCK(o.reserve(nv));
-  if (nrow) HIPCK(hipMemcpyAsync(d.p, rows, nrow * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  HIPCK(launch_finish_supers(d.p, nsup, maxsup, nranks, nv, o.p, ctx->stream));
-  HIPCK(hipMemcpyAsync(out, o.p, nv * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  int rc = sync(ctx);
-  d.release();
-  o.release();
-  return rc;
-}
-
-int mgicp_debug_wave_reduce(mgicp_ctx* ctx, const double* in, int nwaves, double* out_tree, double* out_rs) {
-  if (!ctx || !in || !out_tree || !out_rs || nwaves <= 0) return MGICP_E_INVALID;
-  HIPCK(hipSetDevice(ctx->device));
-  const size_t nin = static_cast<size_t>(nwaves) * 64 * 16, nout = static_cast<size_t>(nwaves) * 16;
-  DevBuf<double> d, t, r;
-  HIPCK(d.reserve(nin));
-  HIPCK(t.reserve(nout));
-  HIPCK(r.reserve(nout));
-  HIPCK(hipMemcpyAsync(d.p, in, nin * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  HIPCK(launch_wave_reduce_check(d.p, nwaves, t.p, r.p, ctx->stream));
-  HIPCK(hipMemcpyAsync(out_tree, t.p, nout * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCK(hipMemcpyAsync(out_rs, r.p, nout * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  int rc = sync(ctx);
-  d.release();
-  t.release();
-  r.release();
-  return rc;
-}
-
-int mgicp_debug_trace(mgicp_ctx* ctx, float* out, int max_iters) {
-  if (!ctx || !out || max_iters < 0) return MGICP_E_INVALID;
-  const int n = static_cast<int>(ctx->trace.size() / 16);
-  const int m = std::min(n, max_iters);
-  std::memcpy(out, ctx->trace.data(), static_cast<size_t>(m) * 16 * sizeof(float));
-  return n;
-}
-
-int mgicp_debug_kernel_times(mgicp_ctx* ctx, double out_ms[MGICP_KERNEL_FAMILIES],
-                             int out_counts[MGICP_KERNEL_FAMILIES]) {
-  if (!ctx || !out_ms) return MGICP_E_INVALID;
-  prof_resolve(ctx);
-  for (int i = 0; i < kFams; ++i) {
-    out_ms[i] = ctx->fam_cnt[i] ? ctx->fam_ms[i] / ctx->fam_cnt[i] : 0.0;
-    if (out_counts) out_counts[i] = ctx->fam_cnt[i];
-  }
-  return MGICP_OK;
-}
-
-int mgicp_set_profiling(mgicp_ctx* ctx, int on) {
-  if (!ctx) return MGICP_E_INVALID;
-  (void)hipSetDevice(ctx->device);
-  cancel_gated(ctx);
-  (void)hipStreamSynchronize(ctx->stream);
-  srv_release(ctx);
-  prof_resolve(ctx);
-  ctx->profiling = on != 0;
-  ctx->prof_tick = 0;
-  for (int i = 0; i < kFams; ++i) {
-    ctx->fam_ms[i] = 0;
-    ctx->fam_cnt[i] = 0;
-  }
-  return MGICP_OK;
-}
-
-// r05 target cache: [0] the current target was adopted from the cache, [1] adoptions and [2] donations
-// on this device so far (process-wide), [3] an entry is cached on this device, [4] the source grid's start
-// from the cached target's cell size (r05; since r06 always 0: the source's grid never depends on the target)
-int mgicp_debug_cache_stats(mgicp_ctx* ctx, long long out[5]) {
-  if (!ctx || !out) return MGICP_E_INVALID;
-  TargetCache& c = g_tcache[ctx->device & 63];
-  std::lock_guard<std::mutex> lk(c.mu);
-  out[0] = ctx->tcache_adopted ? 1 : 0;
-  out[1] = c.hits;
-  out[2] = c.donations;
-  out[3] = c.valid ? 1 : 0;
-  out[4] = 0;  // r06: no speculative source grid any more (the source's grid never depends on the target)
-  return MGICP_OK;
-}
-
 void mgicp_release_cache(void) {
   int dev = 0;
   const bool have = hipGetDevice(&dev) == hipSuccess;
@@ -3817,61 +3019,6 @@ void mgicp_release_cache(void) {
     tcache_clear_locked(c);
   }
   if (have) (void)hipSetDevice(dev);
-}
-
-// Test / diagnostic forms of the engine (INTEGRATION.md "Debug options"): explicit per-context calls,
-// never environment variables, so a deployment cannot switch a kernel by accident.
-// Pending covariance launches are joined and the stream drained first; list-related options drop the
-// target's 1-NN cell lists.
-int mgicp_debug_option(mgicp_ctx* ctx, const char* name, double value) {
-  if (!ctx || !name) return MGICP_E_INVALID;
-  HIPCK(hipSetDevice(ctx->device));
-  int rc = cov_join_all(ctx);
-  if (rc || (rc = sync(ctx))) return rc;
-  const std::string n(name);
-  const bool on = value != 0.0;
-  const int iv = static_cast<int>(value);
-  if (n == "resident") ctx->resident = on;              // resident pass server (else one launch per pass)
-  else if (n == "host_rows") ctx->host_rows = on;       // server supers as stamped host rows (else device total)
-  else if (n == "srv_cus") ctx->srv_cus = std::max(0, iv);  // cap on the server's blocks (0 = every CU)
-  else if (n == "fused_finish") ctx->fused_finish = on; // in-launch reduction finish of launched passes
-  else if (n == "gated") ctx->gated = on;               // launched passes pre-queued behind a command gate
-  else if (n == "async_cov") ctx->async_tgt = on && ctx->aux_stream;  // set_*'s covariance head start
-  else if (n == "lazy_src_cov") {                       // source covariances of accepted points only
-    ctx->lazy_src_cov = on;
-    ctx->src.have_cov = false;
-    ctx->src_lazy_ready = false;
-  } else if (n == "knn_wave") {                         // k-NN: lazy pass + hand-offs one wave per point (1) or per lane (0)
-    ctx->knn_wave = on;
-  } else if (n == "knn_logged") {                       // k-NN: the logged kernel + hand-off (1) or the register-list kernel only (0)
-    ctx->knn_logged = on;
-    ctx->src.have_cov = ctx->tgt.have_cov = false;
-    ctx->src_lazy_ready = false;
-  } else if (n == "vlist") ctx->vlist = on, ctx->vl_valid = false;  // the target's 1-NN cell lists
-  else if (n == "vlist_cold") ctx->vl_cold_groups = std::max(0, iv), ctx->vl_valid = false;
-  else if (n == "vlist_eager") ctx->vl_eager = on, ctx->vl_valid = false;
-  else if (n == "vlist_stats") ctx->vl_stats = on;      // per-sweep list statistics on stderr
-  else if (n == "fuse_compact") ctx->fuse_compact = on; // compaction fused into listed sweeps
-  else if (n == "target_cache") ctx->tcache_on = on;    // adopt / leave the target state (process cache)
-  else if (n == "bar_cmd") {                            // server commands through the BAR (else pinned copy)
-    ctx->bar = on;
-    if (!on && ctx->bar_cmd) {
-      (void)hipFree(ctx->bar_cmd);
-      ctx->bar_cmd = nullptr;
-    }
-    if (on && !ctx->bar_cmd) {
-      hipDeviceProp_t prop;
-      if (hipGetDeviceProperties(&prop, ctx->device) == hipSuccess && prop.isLargeBar &&
-          hipExtMallocWithFlags(reinterpret_cast<void**>(&ctx->bar_cmd), sizeof(PassCmd), hipDeviceMallocFinegrained) ==
-              hipSuccess)
-        HIPCK(hipMemset(ctx->bar_cmd, 0, sizeof(PassCmd)));
-      else
-        ctx->bar_cmd = nullptr;
-    }
-  } else {
-    return fail(ctx, MGICP_E_INVALID, "unknown debug option: " + n);
-  }
-  return MGICP_OK;
 }
 
 }  // extern "C"

@@ -1,15 +1,17 @@
-"""CPU tests of the drop-in boundary: libmgicp.so loads, exports every symbol the C-ABI header
-declares, its ctypes mirrors match the header's structs, and nothing silently falls back to
+"""CPU tests of the drop-in boundary: libmgicp.so loads, exports exactly the symbols its two C-ABI
+headers declare (product and debug), the drop-in needs the product header alone, its ctypes mirrors match the header's structs, and nothing silently falls back to
 CPU compute when no GPU is present."""
 import ctypes
 import os
 import re
+import subprocess
 
 import pytest
 
 from conftest import ROOT
 
 HEADER = os.path.join(ROOT, "include", "mi355x_gicp.h")
+DEBUG_HEADER = os.path.join(ROOT, "include", "mi355x_gicp_debug.h")
 
 
 def _struct_fields(name):
@@ -27,6 +29,12 @@ def _struct_fields(name):
     return fields
 
 
+def _nm(flag, path):
+    """Names `nm <flag> path` lists (last column)."""
+    out = subprocess.run(["nm", *flag.split(), path], capture_output=True, text=True, check=True).stdout
+    return {line.split()[-1] for line in out.splitlines() if line.strip()}
+
+
 def test_library_exports_every_header_symbol():
     from leica_point_cloud_processing_amd import _lib
 
@@ -36,6 +44,22 @@ def test_library_exports_every_header_symbol():
     missing = [s for s in syms if not hasattr(lib, s)]
     assert not missing, missing
     assert set(syms) == set(_lib._SIGNATURES), "ctypes signature table out of sync with the header"
+    # ... and nothing else (csrc/libmgicp.map): no launcher, kernel stub or template instance that another
+    # library of the host process could interpose or collide with
+    exported = _nm("-D --defined-only", _lib.LIB_PATH)
+    assert exported == set(syms), sorted(exported ^ set(syms))
+
+
+def test_headers_split_product_from_debug():
+    """include/mi355x_gicp.h is the drop-in; every test / bench hook is in mi355x_gicp_debug.h."""
+    from leica_point_cloud_processing_amd import _lib
+
+    product = set(_lib.header_symbols(_lib.HEADER_PATH))
+    debug = set(_lib.header_symbols(_lib.DEBUG_HEADER_PATH))
+    assert not product & debug, sorted(product & debug)
+    assert product | debug == set(_lib.header_symbols())
+    assert product and not [s for s in product if s.startswith("mgicp_debug_")]
+    assert debug == {s for s in _lib._SIGNATURES if s.startswith("mgicp_debug_")} | {"mgicp_set_profiling"}
 
 
 @pytest.mark.parametrize("cname,pyname", [("mgicp_params", "MgicpParams"), ("mgicp_result", "MgicpResult")])
@@ -52,11 +76,42 @@ def test_struct_layout_matches_header(cname, pyname):
 
 
 def test_header_is_plain_c():
-    text = open(HEADER).read()
-    assert 'extern "C"' in text
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)  # declarations only, not the docs
-    for banned in ("torch", "hipStream_t", "Eigen", "pcl::", "std::", "#include <hip"):
-        assert banned not in text
+    for header in (HEADER, DEBUG_HEADER):
+        text = open(header).read()
+        assert 'extern "C"' in text, header
+        text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)  # declarations only, not the docs
+        for banned in ("torch", "hipStream_t", "Eigen", "pcl::", "std::", "#include <hip"):
+            assert banned not in text, (header, banned)
+        # each header on its own (the debug header includes what it needs) through a C99 compiler
+        r = subprocess.run(["gcc", "-x", "c", "-std=c99", "-Wall", "-Werror", "-fsyntax-only", header],
+                           capture_output=True, text=True)
+        assert r.returncode == 0, (header, r.stderr)
+
+
+def test_drop_in_uses_the_product_header_only():
+    """What an integrator compiles and links -- the adapter sources and the C-ABI example -- includes
+    mi355x_gicp.h alone, names no debug hook, and its binaries need no mgicp_* symbol outside that header."""
+    import glob
+
+    from leica_point_cloud_processing_amd import _lib
+
+    product = set(_lib.header_symbols(_lib.HEADER_PATH))
+    debug = set(_lib.header_symbols(_lib.DEBUG_HEADER_PATH))
+    adapter = os.path.join(ROOT, "adapter")
+    sources = sorted(glob.glob(os.path.join(adapter, "*.cpp")) + glob.glob(os.path.join(adapter, "*.h")))
+    assert os.path.join(adapter, "cabi_example.cpp") in sources and len(sources) >= 5
+    for path in sources:
+        text = open(path).read()
+        assert "mi355x_gicp_debug.h" not in text, path
+        assert set(re.findall(r'#include\s*[<"]([^">]*mi355x[^">]*)[">]', text)) <= {"mi355x_gicp.h"}, path
+        named = set(re.findall(r"\bmgicp_[a-z_0-9]+", text))
+        assert not named & debug, (path, sorted(named & debug))
+    subprocess.run(["make", "-s", "-C", ROOT, "adapter-example", "adapter-replay", "fod-replay"], check=True,
+                   capture_output=True, text=True)
+    for exe in ("cabi_example", os.path.join("build", "replay_test_gicp_alignment"),
+                os.path.join("build", "replay_test_fod_detector")):
+        needed = {s for s in _nm("-u", os.path.join(adapter, exe)) if s.startswith("mgicp_")}
+        assert needed and needed <= product, (exe, sorted(needed - product))
 
 
 def test_default_params_match_reference():
