@@ -6,10 +6,10 @@ The result is a partition fixed by one predicate on point pairs -- both finite a
 ((dx^2) + dy^2) + dz^2 < float(tolerance^2) -- so the bar is exact equality: clusters, their order
 (size descending, ties by ascending smallest member), members ascending, labels and offsets.
 
-Reference (this file, `_ref_clusters`): candidate pairs from scipy's cKDTree at a slightly widened
-radius, filtered by the exact fp32 predicate (the numpy float32 expression of
-tests/test_fod_filters.py `_bruteforce_keep`), scipy.sparse.csgraph.connected_components, then the size
-filter and the ordering rule.  It is itself checked against an all-pairs brute force with its own
+Reference (tests/cluster_edges_cases.py, `ref_clusters`, shared with the cluster-edge tests): candidate
+pairs from scipy's cKDTree at a slightly widened radius, filtered by the exact fp32 predicate (the numpy
+float32 expression of tests/test_fod_filters.py `_bruteforce_keep`),
+scipy.sparse.csgraph.connected_components, then the size filter and the ordering rule.  It is itself checked against an all-pairs brute force with its own
 union-find.  PCL is not installed here: the order of equal-size clusters beyond 16 clusters is the
 documented stable choice, not pinned against a PCL binary.
 """
@@ -21,108 +21,16 @@ import subprocess
 import numpy as np
 import pytest
 
+from cluster_edges_cases import bruteforce_clusters as _bruteforce_clusters
+from cluster_edges_cases import components as _components
+from cluster_edges_cases import finish as _finish
+from cluster_edges_cases import fod_cloud as _fod_cloud
+from cluster_edges_cases import r2_of as _r2
+from cluster_edges_cases import ref_clusters as _ref_clusters
 from conftest import ROOT
 from leica_point_cloud_processing_amd.cloud import PointCloudRGB
 
 FODREPLAY = os.path.join(ROOT, "adapter", "build", "replay_test_fod_detector")
-
-
-# ---------------------------------------------------------------------------------------
-# the test-side reference
-# ---------------------------------------------------------------------------------------
-def _d2_f32(a, b):
-    """FLANN L2_Simple in fp32, one rounding per operation: ((dx*dx) + dy*dy) + dz*dz."""
-    d = (a.astype(np.float32) - b.astype(np.float32)).astype(np.float32)
-    d2 = ((d[..., 0] * d[..., 0]).astype(np.float32) + (d[..., 1] * d[..., 1]).astype(np.float32)).astype(np.float32)
-    return (d2 + (d[..., 2] * d[..., 2]).astype(np.float32)).astype(np.float32)
-
-
-def _r2(tol):
-    return np.float32(np.float64(tol) * np.float64(tol))
-
-
-def _finish(xyz, fin_idx, comp, min_size, max_size):
-    """components (label per finite point) -> (clusters, labels, offsets, n_components) by the rule."""
-    n = len(xyz)
-    order = np.argsort(comp, kind="stable")  # members ascending inside a component
-    bounds = np.flatnonzero(np.diff(comp[order])) + 1
-    groups = [fin_idx[g] for g in np.split(order, bounds)] if len(order) else []
-    lo, hi = max(int(min_size), 1), (int(max_size) if max_size else np.iinfo(np.int64).max)
-    kept = [g for g in groups if lo <= len(g) <= hi]
-    kept.sort(key=lambda g: (-len(g), int(g[0])))
-    labels = np.full(n, -1, np.int32)
-    for c, g in enumerate(kept):
-        labels[g] = c
-    offsets = np.concatenate([[0], np.cumsum([len(g) for g in kept])]).astype(np.int64)
-    return [g.astype(np.int32) for g in kept], labels, offsets, len(groups)
-
-
-def _components(xyz, tol):
-    from scipy.sparse import coo_matrix
-    from scipy.sparse.csgraph import connected_components
-    from scipy.spatial import cKDTree
-
-    xyz = np.asarray(xyz, np.float32).reshape(-1, 3)
-    fin_idx = np.flatnonzero(np.isfinite(xyz).all(1))
-    pts = xyz[fin_idx]
-    m = len(pts)
-    r2 = _r2(tol)
-    i = j = np.zeros(0, np.int64)
-    if m > 1 and r2 > 0:
-        # every pair the fp32 predicate accepts has an exact distance below tol (1 + 1e-6)
-        cand = cKDTree(pts.astype(np.float64)).query_pairs(float(tol) * (1 + 1e-5) + 1e-30, output_type="ndarray")
-        if len(cand):
-            ok = _d2_f32(pts[cand[:, 0]], pts[cand[:, 1]]) < r2
-            i, j = cand[ok, 0], cand[ok, 1]
-    if m == 0:
-        return fin_idx, np.zeros(0, np.int64)
-    g = coo_matrix((np.ones(len(i), np.int8), (i, j)), shape=(m, m))
-    _, comp = connected_components(g, directed=False)
-    return fin_idx, comp.astype(np.int64)
-
-
-def _ref_clusters(xyz, tol, min_size=1, max_size=0):
-    xyz = np.asarray(xyz, np.float32).reshape(-1, 3)
-    fin_idx, comp = _components(xyz, tol)
-    return _finish(xyz, fin_idx, comp, min_size, max_size)
-
-
-def _bruteforce_clusters(xyz, tol, min_size=1, max_size=0):
-    """All pairs, own union-find: independent of the kd-tree candidates and of csgraph."""
-    xyz = np.asarray(xyz, np.float32).reshape(-1, 3)
-    fin_idx = np.flatnonzero(np.isfinite(xyz).all(1))
-    pts = xyz[fin_idx]
-    m = len(pts)
-    adj = _d2_f32(pts[:, None, :], pts[None, :, :]) < _r2(tol)
-    parent = list(range(m))
-
-    def find(x):
-        while parent[x] != x:
-            parent[x] = parent[parent[x]]
-            x = parent[x]
-        return x
-
-    for a, b in zip(*np.nonzero(np.triu(adj, 1))):
-        ra, rb = find(int(a)), find(int(b))
-        if ra != rb:
-            parent[max(ra, rb)] = min(ra, rb)
-    comp = np.array([find(x) for x in range(m)], np.int64)
-    return _finish(xyz, fin_idx, comp, min_size, max_size)
-
-
-def _fod_cloud(seed=0, n=3000):
-    """The FOD scenario of tests/test_fod_filters.py: a synthetic scan plus 4 foreign-object blobs, with
-    a NaN record and an Inf record."""
-    from leica_point_cloud_processing_amd import synth
-
-    scan, cad, _ = synth.scan_vs_cad(n, 500)
-    rng = np.random.default_rng(seed)
-    blobs = (cad[rng.integers(0, len(cad), 4)][:, None, :] +
-             rng.normal(0, 0.004, (4, 25, 3)) + np.array([0, 0, 0.03])).reshape(-1, 3).astype(np.float32)
-    a = np.concatenate([scan, blobs]).astype(np.float32)
-    a[7] = np.nan
-    a[len(a) - 5, 1] = np.inf
-    return a
 
 
 def _cubes():

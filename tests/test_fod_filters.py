@@ -60,7 +60,7 @@ def test_oracle_segment_differences_matches_bruteforce():
 def _bruteforce_voxels(rec, leaf, min_points=0):
     xyz = np.stack([rec["x"], rec["y"], rec["z"]], 1).astype(np.float32)
     fin = np.isfinite(xyz).all(1)
-    inv = (np.float32(1.0) / np.float32(leaf)).astype(np.float32)
+    inv = (np.float32(1.0) / np.asarray(leaf, np.float32)).astype(np.float32)  # one leaf or one per axis
     mn, mx = xyz[fin].min(0), xyz[fin].max(0)
     min_b = np.floor(mn * inv).astype(np.int64)
     div = np.floor(mx * inv).astype(np.int64) - min_b + 1
