@@ -36,6 +36,12 @@ int mgicp_debug_fdf(mgicp_ctx* ctx, const double x[6], double* f, double g6[6]);
  * NULL) (a "detached" shard, no RCCL) they cover rank r's source range only, so sharding can
  * be verified on one device; align/fitness refuse to run in that mode. */
 int mgicp_debug_fdf_sums(mgicp_ctx* ctx, const double x[6], double out16[16]);
+/* n objective passes at the states xs[6 k .. 6 k + 5] as ONE BFGS run makes them: a single resident
+ * server (when the shard is servable) launched with the first pass, commanded n times and cancelled
+ * after the last, so passes 2 .. n run on a live server with its chunks resident and its host rows
+ * alternating between the two parity buffers (mgicp_debug_fdf_sums tears the server down after its
+ * one pass).  out16n[16 k ..]: the sums of pass k, as mgicp_debug_fdf_sums.  1 <= n <= 4096. */
+int mgicp_debug_fdf_sums_run(mgicp_ctx* ctx, const double* xs, int n, double* out16n);
 /* Objective-pass timing (bench.py's roofline leg): npasses passes at state x over the last
  * correspondence sweep, back to back on the device, bracketed by HIP events on the context's
  * stream.  mode 0: the resident pass server (one launch running all passes; the pass

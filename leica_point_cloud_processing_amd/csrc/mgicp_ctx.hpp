@@ -474,8 +474,10 @@ int moments_pass(mgicp_ctx* ctx, const Mat4& T, const Mat4& G, bool supers_only 
 int fitness_supers(mgicp_ctx* ctx, const Mat4& T, double max_range);
 // over the engine's DeviceFunctor (one run of it, no queued pass or live server left behind):
 // OptimizationFunctorWithIndices::fdf at x over the last correspondence sweep, and the 16 raw sums of
-// one objective pass at x
+// one objective pass at x; fdf_sums_run_at: n passes at xs[0 .. n) over ONE DeviceFunctor (one live
+// server for all of them, as a BFGS run holds it), kRedVals sums per pass
 int fdf_at(mgicp_ctx* ctx, const Vec6& x, double& f, Vec6& g);
 int fdf_sums_at(mgicp_ctx* ctx, const Vec6& x, double sums[kRedVals]);
+int fdf_sums_run_at(mgicp_ctx* ctx, const Vec6* xs, int n, double* sums);
 
 }  // namespace mgicp

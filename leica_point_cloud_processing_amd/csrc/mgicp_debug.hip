@@ -213,6 +213,15 @@ int mgicp_debug_fdf_sums(mgicp_ctx* ctx, const double x[6], double out16[16]) {
   return fdf_sums_at(ctx, xv, out16);
 }
 
+int mgicp_debug_fdf_sums_run(mgicp_ctx* ctx, const double* xs, int n, double* out16n) {
+  if (!ctx || !xs || !out16n || n < 1 || n > 4096 || !ctx->have_corr) return MGICP_E_INVALID;
+  HIPCK(hipSetDevice(ctx->device));
+  std::vector<Vec6> xv(static_cast<size_t>(n));
+  for (int k = 0; k < n; ++k)
+    for (int i = 0; i < 6; ++i) xv[k][i] = xs[6 * k + i];
+  return fdf_sums_run_at(ctx, xv.data(), n, out16n);
+}
+
 int mgicp_debug_pass_bench(mgicp_ctx* ctx, const double x[6], int npasses, int mode, double* out_ms,
                            double out16[16]) {
   if (!ctx || !x || npasses < 1 || npasses > 100000 || (mode != 0 && mode != 1) || !ctx->have_corr)

@@ -1932,6 +1932,15 @@ int mgicp::fdf_sums_at(mgicp_ctx* ctx, const Vec6& x, double sums[kRedVals]) {
   DeviceFunctor fn{ctx};
   return fn.pass(x, sums);
 }
+int mgicp::fdf_sums_run_at(mgicp_ctx* ctx, const Vec6* xs, int n, double* sums) {
+  GateGuard guard{ctx};  // the server launched by the first pass serves them all, then is cancelled
+  DeviceFunctor fn{ctx};
+  for (int k = 0; k < n; ++k) {
+    int rc = fn.pass(xs[k], sums + static_cast<size_t>(k) * kRedVals);
+    if (rc) return rc;
+  }
+  return MGICP_OK;
+}
 namespace {
 
 // every error return of an align (a HIP error mid-loop, MGICP_E_COMM from a quitting rank, ...) drains

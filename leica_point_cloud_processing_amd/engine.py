@@ -404,6 +404,14 @@ class GICPEngine:
         self._check(self._lib.mgicp_debug_fdf_sums(self._h, _dp(x), _dp(out)), "debug_fdf_sums")
         return out
 
+    def debug_fdf_sums_run(self, xs) -> np.ndarray:
+        """(n, 16) sums of n passes at the states xs (n, 6) run as one BFGS run makes them: one live
+        server for all of them (mgicp_debug_fdf_sums_run)"""
+        xs = np.ascontiguousarray(np.asarray(xs, np.float64).reshape(-1, 6))
+        out = np.zeros((len(xs), 16), np.float64)
+        self._check(self._lib.mgicp_debug_fdf_sums_run(self._h, _dp(xs), len(xs), _dp(out)), "debug_fdf_sums_run")
+        return out
+
     def debug_wave_reduce(self, vals) -> tuple:
         """(shuffle-tree sums, reduce-scatter sums) of vals[w][64][16] per wave w (the chunk reduction)"""
         vals = np.ascontiguousarray(vals, np.float64)

@@ -429,6 +429,7 @@ static float* copy_xyz(const float* xyz, size_t n, size_t stride, int* bad) {
 int ref_set_source(ref_gicp* g, const float* xyz, size_t n, size_t stride) {
     if (!g || (!xyz && n) || stride < 12) return REF_E_INVALID;
     free_sum_order(g);  /* a stream order belongs to one source cloud */
+    free_scratch(g);    /* and so do the sweep's buffers, sized by its point count (ref_correspondences) */
     int bad;
     free(g->src);
     g->src = copy_xyz(xyz, n, stride, &bad);

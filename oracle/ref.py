@@ -2,6 +2,13 @@
 
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this module,
 and only as the checker / the timed CPU baseline -- never as a compute path of the product.
+
+Order of calls on one RefGICP object: set_mahalanobis_upper acts AT THE SWEEP (the matrices are built and
+stored there), so set it before correspondences() / align(); set after a sweep it changes nothing until
+the next one.  set_sum_order only steers the sums (fdf, fdf_mode_sums, align) and may be set before or
+after the sweep, but belongs to one source: set_source drops it, together with the previous source's
+sweep (correspondences() is needed again before fdf / fdf_mode_sums / moments).  One object may be given
+sources of any sizes in turn.
 """
 from __future__ import annotations
 
