@@ -3,7 +3,8 @@ HIPCC ?= /opt/rocm/bin/hipcc
 ARCH  ?= gfx950
 PKG   := leica_point_cloud_processing_amd
 LIB   := $(PKG)/libmgicp.so
-SRCS  := $(PKG)/csrc/mgicp_kernels.hip $(PKG)/csrc/mgicp_engine.hip $(PKG)/csrc/mgicp_debug.hip
+SRCS  := $(PKG)/csrc/mgicp_kernels.hip $(PKG)/csrc/mgicp_engine.hip $(PKG)/csrc/mgicp_clouds.hip \
+         $(PKG)/csrc/mgicp_pass.hip $(PKG)/csrc/mgicp_fod.hip $(PKG)/csrc/mgicp_comm.hip $(PKG)/csrc/mgicp_debug.hip
 HDRS  := $(wildcard $(PKG)/csrc/*.hpp) include/mi355x_gicp.h include/mi355x_gicp_debug.h
 # the export map: the library's dynamic symbols are the mgicp_* functions of the two headers, all else local
 MAP   := $(PKG)/csrc/libmgicp.map
@@ -14,7 +15,8 @@ HIPFLAGS := -O3 -std=c++17 --offload-arch=$(ARCH) -fPIC -ffp-contract=off -Wall 
 all: $(LIB) oracle adapter-example adapter-replay fod-replay
 
 OBJDIR := $(PKG)/csrc/build
-OBJS  := $(OBJDIR)/mgicp_kernels.o $(OBJDIR)/mgicp_engine.o $(OBJDIR)/mgicp_debug.o
+OBJS  := $(OBJDIR)/mgicp_kernels.o $(OBJDIR)/mgicp_engine.o $(OBJDIR)/mgicp_clouds.o $(OBJDIR)/mgicp_pass.o \
+         $(OBJDIR)/mgicp_fod.o $(OBJDIR)/mgicp_comm.o $(OBJDIR)/mgicp_debug.o
 
 # one object per source (make -j compiles them side by side; an engine edit does not rebuild the kernels)
 $(OBJDIR)/%.o: $(PKG)/csrc/%.hip $(HDRS)

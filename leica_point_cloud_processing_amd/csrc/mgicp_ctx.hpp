@@ -1,12 +1,16 @@
-// mgicp_ctx.hpp -- the context and the host helpers that libmgicp.so's two host translation units share:
-// mgicp_engine.hip (the product calls of include/mi355x_gicp.h) and mgicp_debug.hip (the test, benchmark
-// and diagnostic calls of include/mi355x_gicp_debug.h).  Private: nothing here crosses the C-ABI, and the
+// mgicp_ctx.hpp -- the context and the host helpers that libmgicp.so's host translation units share:
+// mgicp_engine.hip, mgicp_clouds.hip, mgicp_pass.hip, mgicp_fod.hip and mgicp_comm.hip (the product calls
+// of include/mi355x_gicp.h, by subsystem) and mgicp_debug.hip (the test, benchmark and diagnostic calls
+// of include/mi355x_gicp_debug.h).  Private: nothing here crosses the C-ABI, and the
 // export map (libmgicp.map) keeps every name below out of the library's dynamic symbol table.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <mutex>
@@ -76,7 +80,7 @@ struct Graveyard {
   }
 };
 // r06: a device allocation that fails for lack of memory first evicts the process-wide
-// target cache's entry of the current device (set in mgicp_engine.hip, next to the cache) and retries once
+// target cache's entry of the current device (set in mgicp_clouds.hip, next to the cache) and retries once
 extern bool (*g_oom_evict)();
 // the graveyard of the context being constructed: every DevBuf member of a mgicp_ctx picks it up
 extern thread_local Graveyard* t_new_ctx_grave;
@@ -453,31 +457,123 @@ struct RowView {
   }
 };
 
-// ---- host helpers defined in mgicp_engine.hip (documented there) that the debug entry points call too ----
+inline double now_ms() {
+  return std::chrono::duration<double, std::milli>(
+             std::chrono::steady_clock::now().time_since_epoch())
+      .count();
+}
+
+// MGICP_TRACE=1: phase timestamps of uploads and grid builds on stderr (host-time diagnosis)
+inline bool trace_on() {
+  static const int on = [] {
+    const char* t = std::getenv("MGICP_TRACE");
+    return t && std::atoi(t) != 0 ? 1 : 0;
+  }();
+  return on != 0;
+}
+#define MGICP_TRACE_AT(label)                                                  \
+  do {                                                                         \
+    if (trace_on()) std::fprintf(stderr, "[mgicp] %10.3f ms  %s\n", now_ms(), label); \
+  } while (0)
+
+// objective-pass event sampling while profiling: every 8th launch (identical work per launch, and two
+// event records per pass would cost ~4 % of the PCL-mode align)
+constexpr unsigned kProfStride = 8;
+
+inline hipEvent_t ev_get(mgicp_ctx* ctx) {
+  if (!ctx->pool.empty()) {
+    hipEvent_t e = ctx->pool.back();
+    ctx->pool.pop_back();
+    return e;
+  }
+  hipEvent_t e = nullptr;
+  (void)hipEventCreate(&e);
+  return e;
+}
+
+struct ProfScope {
+  mgicp_ctx* ctx;
+  int fam;
+  hipEvent_t a = nullptr;
+  ProfScope(mgicp_ctx* c, int f) : ctx(c), fam(f) {
+    // objective passes are sampled (every kProfStride-th launch); the rest are all timed
+    if (ctx->profiling && (fam != kFamFdf || (ctx->prof_tick++ % kProfStride) == 0)) {
+      a = ev_get(ctx);
+      (void)hipEventRecord(a, ctx->stream);
+    }
+  }
+  ~ProfScope() {
+    if (a) {
+      hipEvent_t b = ev_get(ctx);
+      (void)hipEventRecord(b, ctx->stream);
+      ctx->pending.push_back({a, b, fam});
+    }
+  }
+};
+
+// ---- mgicp_pass.hip: the objective passes and their transport (documented there) ----
 Mat4 apply_state(const Vec6& x);
 void prof_resolve(mgicp_ctx* ctx);
 void cancel_gated(mgicp_ctx* ctx);
+void srv_resolve(mgicp_ctx* ctx);
 void srv_release(mgicp_ctx* ctx);
 int sync(mgicp_ctx* ctx);
-int cov_join_all(mgicp_ctx* ctx);
-int compute_cov(mgicp_ctx* ctx, Cloud& cl, size_t p0, size_t p1, size_t stride = 0);
-int prepare(mgicp_ctx* ctx, bool need_cov);
+int reset_stamps(mgicp_ctx* ctx);
 int ensure_host_red(mgicp_ctx* ctx);
 CorrSoA corr_soa(mgicp_ctx* ctx);
 RowView row_view(const mgicp_ctx* ctx);
 int ensure_rows(mgicp_ctx* ctx);
 int wait_rows(mgicp_ctx* ctx, unsigned int rstamp, const Xf34& A, double out[kRedVals], bool allow_takeover);
 int ensure_iter_buffers(mgicp_ctx* ctx);
-int set_output(mgicp_ctx* ctx, const Mat4& G);
-int correspond(mgicp_ctx* ctx, const Mat4& T, const Mat4& G, bool seed);
-int moments_pass(mgicp_ctx* ctx, const Mat4& T, const Mat4& G, bool supers_only = false);
-int fitness_supers(mgicp_ctx* ctx, const Mat4& T, double max_range);
-// over the engine's DeviceFunctor (one run of it, no queued pass or live server left behind):
+int combine_to_host(mgicp_ctx* ctx, int nv, const double* sup, double* out);
+// OptimizationFunctorWithIndices::fdf on the device; memoises the last state
+struct DeviceFunctor {
+  mgicp_ctx* ctx;
+  bool have_memo = false;
+  Vec6 memo_x{};
+  double memo_f = 0;
+  Vec6 memo_g{};
+  double m = 0;  // correspondences of this sweep (all ranks)
+
+  int pass(const Vec6& x, double sums[kRedVals]);         // one objective pass at x: its 16 raw sums
+  void memoise(const Vec6& x, const double s[kRedVals]);  // f and g at x from the sums of the pass at x
+  int eval(const Vec6& x, double& f, Vec6& g);
+};
+struct GateGuard {  // a BFGS run leaves no gated pass queued behind it
+  mgicp_ctx* ctx;
+  ~GateGuard() { cancel_gated(ctx); }
+};
+// over one DeviceFunctor (one run of it, no queued pass or live server left behind):
 // OptimizationFunctorWithIndices::fdf at x over the last correspondence sweep, and the 16 raw sums of
 // one objective pass at x; fdf_sums_run_at: n passes at xs[0 .. n) over ONE DeviceFunctor (one live
 // server for all of them, as a BFGS run holds it), kRedVals sums per pass
 int fdf_at(mgicp_ctx* ctx, const Vec6& x, double& f, Vec6& g);
 int fdf_sums_at(mgicp_ctx* ctx, const Vec6& x, double sums[kRedVals]);
 int fdf_sums_run_at(mgicp_ctx* ctx, const Vec6* xs, int n, double* sums);
+
+// ---- mgicp_clouds.hip: uploads, grids, covariances, the target cache (documented there) ----
+int upload_cloud(mgicp_ctx* ctx, Cloud& cl, const float* xyz, size_t n, size_t stride, bool device_ptr);
+int bbox_to_host(mgicp_ctx* ctx, const float4* pts, size_t n, float lo[3], float hi[3], double* bad = nullptr,
+                 const char* queued = nullptr);
+int build_grid(mgicp_ctx* ctx, Cloud& cl, bool defer_extras = false);
+const uint32_t* query_perm(mgicp_ctx* ctx);
+int cov_join_all(mgicp_ctx* ctx);
+int cov_prep_async_all(mgicp_ctx* ctx);
+int compute_cov(mgicp_ctx* ctx, Cloud& cl, size_t p0, size_t p1, size_t stride = 0);
+int target_cov(mgicp_ctx* ctx);
+int cov_lazy(mgicp_ctx* ctx);
+void tcache_donate(mgicp_ctx* ctx, bool cov_complete);
+int tcache_adopt(mgicp_ctx* ctx);
+
+// ---- mgicp_engine.hip: the align loop's steps that the debug entry points call too (documented there) ----
+int prepare(mgicp_ctx* ctx, bool need_cov);
+int set_output(mgicp_ctx* ctx, const Mat4& G);
+int correspond(mgicp_ctx* ctx, const Mat4& T, const Mat4& G, bool seed);
+int moments_pass(mgicp_ctx* ctx, const Mat4& T, const Mat4& G, bool supers_only = false);
+int fitness_supers(mgicp_ctx* ctx, const Mat4& T, double max_range);
+
+// ---- mgicp_comm.hip: the xGMI row exchange's teardown ----
+void xgmi_cancel(mgicp_ctx* ctx);
+void xgmi_detach(mgicp_ctx* ctx);
 
 }  // namespace mgicp
