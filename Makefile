@@ -12,7 +12,7 @@ LDMAP := -Wl,--version-script=$(MAP)
 # -ffp-contract=off: no FMA contraction, so fp32/fp64 expressions round like PCL's SSE2 Eigen
 HIPFLAGS := -O3 -std=c++17 --offload-arch=$(ARCH) -fPIC -ffp-contract=off -Wall -Wno-unused-result
 
-all: $(LIB) oracle adapter-example adapter-replay fod-replay
+all: $(LIB) oracle adapter-example adapter-replay fod-replay normals-replay
 
 OBJDIR := $(PKG)/csrc/build
 OBJS  := $(OBJDIR)/mgicp_kernels.o $(OBJDIR)/mgicp_engine.o $(OBJDIR)/mgicp_clouds.o $(OBJDIR)/mgicp_pass.o \
@@ -67,6 +67,20 @@ $(FODREPLAY): adapter/FODDetector_mi355x.cpp include/mi355x_gicp.h $(wildcard $(
 
 fod-replay: $(FODREPLAY)
 
+# adapter/Utils_mi355x.cpp (Utils::getNormals) compiled the same way, against the stand-ins above with the
+# Utils.h of tests/adapter_standins_normals in front (getNormals and a layout-exact pcl::Normal), linked
+# with a driver that runs it as InitialAlignment's constructor does (test infrastructure)
+STANDIN_NRM := tests/adapter_standins_normals
+NRMREPLAY   := adapter/build/replay_test_normals
+$(NRMREPLAY): adapter/Utils_mi355x.cpp include/mi355x_gicp.h $(wildcard $(STANDIN)/*.h) \
+              $(wildcard $(STANDIN_NRM)/*.h) $(STANDIN)/Utils_standin.cpp $(STANDIN_NRM)/replay_test_normals.cpp $(LIB)
+	mkdir -p adapter/build
+	g++ -O2 -std=c++14 -Wall -Wextra -Werror -I$(STANDIN_NRM) -I$(STANDIN) -Iadapter -Iinclude -o $@ \
+	    adapter/Utils_mi355x.cpp $(STANDIN)/Utils_standin.cpp $(STANDIN_NRM)/replay_test_normals.cpp \
+	    -L$(PKG) -lmgicp -Wl,-rpath,'$$ORIGIN/../../$(PKG)'
+
+normals-replay: $(NRMREPLAY)
+
 oracle:
 	$(MAKE) -C oracle
 
@@ -74,4 +88,4 @@ clean:
 	rm -f $(LIB) $(PKG)/libmgicp_*.so $(OBJS)
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle clean adapter-example adapter-replay fod-replay variant
+.PHONY: all oracle clean adapter-example adapter-replay fod-replay normals-replay variant

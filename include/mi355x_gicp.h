@@ -138,6 +138,41 @@ int mgicp_cloud_resolution(mgicp_ctx* ctx, const float* xyz, size_t n, size_t st
 int mgicp_radius_filter(mgicp_ctx* ctx, const float* xyz, size_t n, size_t stride_bytes,
                         double radius, int min_neighbors, unsigned char* keep);
 
+/* Utils::getNormals (src/Utils.cpp:27-44; InitialAlignment.cpp:69-70 and GICPAlignment::getCovariances
+ * call it): pcl::NormalEstimation<PointXYZRGB, Normal> with a radius search, PCL 1.8.1
+ * computeFeature / computePointNormal restated.  The neighbour set of record i is every finite record
+ * j (i included) with FLANN's float ((dx^2) + dy^2) + dz^2 < float(radius^2), strict -- the test of the
+ * radius filter above; n_neighbors[i] is its size (exact; 0 for a non-finite record).  A non-finite
+ * record, or one whose set holds fewer than 3 points, gets normal (NaN, NaN, NaN) and curvature NaN:
+ * exactly the records with keep = 0 from mgicp_radius_filter(..., radius, 3, keep).  Otherwise: the
+ * covariance C = S / m - mu mu' of the set from fp64 sums of the fp64 differences p_j - q_i, added in
+ * grid order by one lane (the same bits every call; PCL's float raw moments about the origin in
+ * FLANN's order are NOT reproduced, DESIGN.md "Radius normals"); the normal is the unit eigenvector
+ * of C's smallest eigenvalue (fp64 Jacobi), the curvature |lambda_min / trace(C)| (0 when the trace is
+ * 0); both are rounded to float and the normal is flipped when (viewpoint - q_i) . n < 0
+ * (flipNormalTowardsViewpoint; viewpoint NULL: (0, 0, 0), PCL's default).  A set whose points are all
+ * identical or collinear has no plane: its normal is NaN or some unit vector, no direction promised.
+ * x, y, z go to byte offsets 0/4/8 of records of normal_stride_bytes (>= 12, a multiple of 4; 32 for
+ * pcl::Normal, whose curvature at offset 16 the caller copies from the packed array), other bytes
+ * untouched.  float(radius^2) = 0 links nothing: every record NaN, every count 0.  radius negative or
+ * NaN, a bad pointer or stride: MGICP_E_INVALID; n = 0: OK.
+ * Uses the helper cloud slot: a set source / target and their cached state stay as they are.
+ * Single rank: with a communicator attached it runs locally, without a collective. */
+typedef struct {
+    double n_finite;     /* finite records (the searched tree) */
+    double n_nan;        /* records that received a NaN normal */
+    double pair_tests;   /* point-pair distance evaluations the device made */
+    double ms_grid;      /* host call -> grid of the finite records built (upload included) */
+    double ms_device;    /* first launch -> stream synchronise after the last */
+    double ms_total;     /* host call -> outputs written */
+} mgicp_normals_info;
+int mgicp_estimate_normals(mgicp_ctx* ctx, const float* xyz, size_t n, size_t stride_bytes,
+                           double radius, const float viewpoint[3] /* NULL: (0,0,0) */,
+                           float* normals, size_t normal_stride_bytes,
+                           float* curvature /* may be NULL, packed n */,
+                           int* n_neighbors /* may be NULL, packed n */,
+                           mgicp_normals_info* info /* may be NULL */);
+
 /* ---- the FOD-side callers either side of the GICP path ----
  * pcl::SegmentDifferences<PointXYZRGB>::segment as called by Filter::removeFromCloud
  * (src/Filter.cpp:176-189) on the cloud the FSM just transformed with

@@ -1,5 +1,6 @@
 // mgicp_fod.hip -- the product calls beside the alignment (include/mi355x_gicp.h): point transforms,
-// cloud resolution, the radius filter, segment differences, Euclidean clustering and the voxel grid.
+// cloud resolution, the radius filter, radius normals, segment differences, Euclidean clustering and the
+// voxel grid.
 #pragma clang fp contract(off)
 
 #include <hip/hip_runtime.h>
@@ -138,6 +139,71 @@ int mgicp_radius_filter(mgicp_ctx* ctx, const float* xyz, size_t n, size_t strid
   HIPCK(launch_radius_keep(ctx->aux.view, ctx->aux.n, r2, min_neighbors, d_keep.p, ctx->stream));
   HIPCK(hipMemcpyAsync(keep, d_keep.p, n, hipMemcpyDeviceToHost, ctx->stream));
   return sync(ctx);
+}
+
+int mgicp_estimate_normals(mgicp_ctx* ctx, const float* xyz, size_t n, size_t stride, double radius,
+                           const float viewpoint[3], float* normals, size_t normal_stride, float* curvature,
+                           int* n_neighbors, mgicp_normals_info* info) {
+  if (!ctx || !(radius >= 0) || (n && (!xyz || !normals)) || stride < 12 || (stride % 4) || normal_stride < 12 ||
+      (normal_stride % 4))
+    return MGICP_E_INVALID;
+  HIPCK(hipSetDevice(ctx->device));
+  const double t0 = now_ms();
+  mgicp_normals_info inf{};
+  if (info) *info = inf;
+  if (n == 0) return MGICP_OK;
+  // FLANN's radius: float(radius^2), strict.  0 links nothing, not even a point with itself
+  const float r2 = static_cast<float>(radius * radius);
+  // every neighbour lies within `reach` per axis; a denormal r2 may be far above radius^2
+  double reach = radius;
+  if (r2 < 1.17549435e-38f) reach = std::max(reach, std::sqrt(static_cast<double>(r2)));
+  // the tree holds the finite records only: grid over those, at a cell edge of one radius (a query's
+  // neighbours then lie in a block of about 3 x 3 x 3 cells; the kernel is exact for any edge)
+  int rc = aux_grid(ctx, xyz, n, stride, r2 > 0.f ? std::min(reach, 1e30) : 0.0);
+  if (rc) return rc;
+  const double t1 = now_ms();
+  const size_t nf = ctx->aux.n;
+  hipStream_t s = ctx->stream;
+  ScopedBuf<float4> d_out;
+  ScopedBuf<int> d_cnt;
+  HIPCK(d_out.reserve(n));
+  HIPCK(d_cnt.reserve(n));
+  HIPCK(ctx->cc_tests.reserve(1));
+  const float vp[3] = {viewpoint ? viewpoint[0] : 0.f, viewpoint ? viewpoint[1] : 0.f, viewpoint ? viewpoint[2] : 0.f};
+  const double t2 = now_ms();
+  // records outside the grid (non-finite) keep these: a quiet NaN in every component, no neighbour
+  HIPCK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_out.p), 0x7fc00000, n * 4, s));
+  HIPCK(hipMemsetAsync(d_cnt.p, 0, n * sizeof(int), s));
+  HIPCK(hipMemsetAsync(ctx->cc_tests.p, 0, sizeof(unsigned long long), s));
+  HIPCK(launch_normals_tile(ctx->aux.view, nf, r2, vp, d_out.p, d_cnt.p, ctx->cc_tests.p, s));
+  if ((rc = sync(ctx))) return rc;
+  const double t3 = now_ms();
+  std::vector<float4> ho(n);
+  std::vector<int> hc(n_neighbors ? 0 : n);
+  int* cnt = n_neighbors ? n_neighbors : hc.data();
+  unsigned long long ntests = 0;
+  HIPCK(hipMemcpyAsync(ho.data(), d_out.p, n * sizeof(float4), hipMemcpyDeviceToHost, s));
+  HIPCK(hipMemcpyAsync(cnt, d_cnt.p, n * sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCK(hipMemcpyAsync(&ntests, ctx->cc_tests.p, sizeof(ntests), hipMemcpyDeviceToHost, s));
+  if ((rc = sync(ctx))) return rc;
+  unsigned char* base = reinterpret_cast<unsigned char*>(normals);
+  size_t n_nan = 0;
+  for (size_t i = 0; i < n; ++i) {
+    float* o = reinterpret_cast<float*>(base + i * normal_stride);
+    o[0] = ho[i].x;
+    o[1] = ho[i].y;
+    o[2] = ho[i].z;
+    if (curvature) curvature[i] = ho[i].w;
+    n_nan += !(ho[i].x == ho[i].x && ho[i].y == ho[i].y && ho[i].z == ho[i].z);
+  }
+  inf.n_finite = static_cast<double>(nf);
+  inf.n_nan = static_cast<double>(n_nan);
+  inf.pair_tests = static_cast<double>(ntests);
+  inf.ms_grid = t1 - t0;
+  inf.ms_device = t3 - t2;
+  inf.ms_total = now_ms() - t0;
+  if (info) *info = inf;
+  return MGICP_OK;
 }
 
 int mgicp_segment_differences(mgicp_ctx* ctx, const float T_cm[16], const float* in, size_t n,

@@ -333,6 +333,14 @@ hipError_t launch_cc_link(const GridView& g, size_t n, const uint32_t* keys_sort
 hipError_t launch_cc_labels(const GridView& g, const uint32_t* perm, size_t n, uint32_t* parent, uint32_t* root,
                             uint32_t* min_orig, uint32_t* keys, uint32_t* vals, hipStream_t s);
 
+// NormalEstimation with a radius search (Utils::getNormals): for every grid point, over its neighbours
+// "float d2 < r2" (itself included), the normal (x, y, z) and curvature (w) of out[original index] and
+// their number in count[original index]; fewer than 3: four NaNs.  out / count hold one entry per
+// original record (the caller presets those of records outside the grid).  *pair_tests (zeroed by the
+// caller) += distance evaluations.  Exact for any cell edge; fastest with an edge near the radius.
+hipError_t launch_normals_tile(const GridView& g, size_t n, float r2, const float vp[3], float4* out, int* count,
+                               unsigned long long* pair_tests, hipStream_t s);
+
 #if defined(MGICP_CORR_PHASES) && MGICP_CORR_PHASES
 hipError_t corr_phase_take(unsigned long long out[24]);  // diagnostic builds: read and reset
 #endif

@@ -3450,6 +3450,205 @@ __global__ void radius_keep_kernel(GridView g, size_t n, float r2, int need,
   keep_orig[__float_as_uint(q.w)] = vis.count >= need ? 1 : 0;
 }
 
+// ------------------------------------------------------------------------------------
+// Radius normals (pcl::NormalEstimation with a radius search, as Utils::getNormals calls it):
+// the cell-cooperative, LDS-staged tile search -- DESIGN.md "Radius normals".
+// ------------------------------------------------------------------------------------
+// A block owns kNrmThreads consecutive sorted positions, one query per lane.  The sort is by cell
+// (z, then y, then x), so those queries are a few runs of x-adjacent cells.  The block takes them
+// group by group: a group is the run of its queries that share the leader's cell row (y, z) and lie
+// within kNrmRunCells cells of the leader along x.  For a group the block
+//   1. reduces the bounding box of the group's query coordinates,
+//   2. widens it by rx = sqrtf(r2) * 1.0001f + slop and takes the cells of its corners (bcell, the very
+//      function that assigned every point its cell): the group's cell box,
+//   3. streams the box's rows -- each one contiguous range of pts -- through the LDS stage in chunks of
+//      kNrmStage points (16-byte loads, rows packed back to back), and after each chunk every lane of
+//      the group tests the staged points against its own query: one LDS address per wave (broadcast).
+// Exactness of the cell box, for any h (DESIGN.md has the long form): a pair passes the float test only
+// if dx^2 < r2 as real numbers for the ROUNDED difference dx = fl(q.x - p.x) (rounding is monotone and
+// r2 is a float), so |dx| < sqrt(r2) <= sqrtf(r2) (1 + 2^-24) and |q.x - p.x| <= |dx| (1 + 2^-24).  With
+// lo <= q.x the float fl(lo - rx) is at most p.x: the 1e-4 margin covers the three roundings relative
+// to rx, the slop (>= 2^-20 of the largest coordinate) the rounding of the difference relative to lo.
+// bcell is monotone (a rounded subtraction, a rounded product by inv_h > 0, floor, clamps), so
+// bcell(p.x) >= bcell(fl(lo - rx)); the upper side and the other axes alike.  An infinite rx gives
+// the whole grid.
+// Order of the sums: rows ascend in z then y and positions ascend within a row, so a lane meets its
+// neighbours in ascending sorted position whatever the grouping and chunking -- the same bits every call.
+constexpr int kNrmThreads = 64;   // queries per block: one wave (measured against 128 and 256)
+constexpr int kNrmStage = 512;    // points per staged chunk (8 KiB of LDS)
+constexpr int kNrmRunCells = 3;  // x-adjacent cells one group may span
+constexpr int kNrmBatch = 8;     // staged points a lane reads and tests before it adds the hits
+
+__device__ __forceinline__ int nrm_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+
+__global__ __launch_bounds__(kNrmThreads) void normals_tile_kernel(GridView g, size_t n, float r2, float vx, float vy,
+                                                                   float vz, float4* __restrict__ out_orig,
+                                                                   int* __restrict__ count_orig,
+                                                                   unsigned long long* __restrict__ pair_tests) {
+  __shared__ float4 stage[kNrmStage];
+  __shared__ float box[kNrmThreads / 64][6];
+  __shared__ int lead[3];
+  const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
+  const size_t p0 = static_cast<size_t>(blockIdx.x) * kNrmThreads;
+  if (p0 >= n) return;  // whole block
+  const int nq = static_cast<int>(n - p0 < static_cast<size_t>(kNrmThreads) ? n - p0 : kNrmThreads);
+  const bool valid = t < nq;
+  const float4 q = g.pts[valid ? p0 + t : p0];
+  const int cx = bcell(q.x, g.ox, g.inv_h, g.nx), cy = bcell(q.y, g.oy, g.inv_h, g.ny),
+            cz = bcell(q.z, g.oz, g.inv_h, g.nz);
+  const double qx = static_cast<double>(q.x), qy = static_cast<double>(q.y), qz = static_cast<double>(q.z);
+  const float rx = sqrtf(r2) * 1.0001f + g.slop;
+  // first moments s0..s2 and second moments (xx xy xz yy yz zz) of p - q over the neighbours
+  double s0 = 0.0, s1 = 0.0, s2 = 0.0, sxx = 0.0, sxy = 0.0, sxz = 0.0, syy = 0.0, syz = 0.0, szz = 0.0;
+  int m = 0;
+  unsigned long long tests = 0;  // per wave (every lane holds the wave's count)
+  int cur = 0;
+  while (cur < nq) {  // one group per turn; every value that steers a barrier is one per block
+    if (t == cur) {
+      lead[0] = cx;
+      lead[1] = cy;
+      lead[2] = cz;
+    }
+    __syncthreads();
+    const bool in = valid && t >= cur && cy == lead[1] && cz == lead[2] && cx < lead[0] + kNrmRunCells;
+    float lo[3] = {in ? q.x : INFINITY, in ? q.y : INFINITY, in ? q.z : INFINITY};
+    float hi[3] = {in ? q.x : -INFINITY, in ? q.y : -INFINITY, in ? q.z : -INFINITY};
+#pragma unroll
+    for (int k = 32; k > 0; k >>= 1) {
+#pragma unroll
+      for (int d = 0; d < 3; ++d) {
+        lo[d] = fminf(lo[d], __shfl_xor(lo[d], k));
+        hi[d] = fmaxf(hi[d], __shfl_xor(hi[d], k));
+      }
+    }
+    if (lane == 0) {
+#pragma unroll
+      for (int d = 0; d < 3; ++d) {
+        box[wid][d] = lo[d];
+        box[wid][3 + d] = hi[d];
+      }
+    }
+    const int members = __syncthreads_count(in ? 1 : 0);  // >= 1: the leader
+#pragma unroll
+    for (int w = 0; w < kNrmThreads / 64; ++w) {
+#pragma unroll
+      for (int d = 0; d < 3; ++d) {
+        lo[d] = fminf(lo[d], box[w][d]);
+        hi[d] = fmaxf(hi[d], box[w][3 + d]);
+      }
+    }
+    const int xa = nrm_uniform(bcell(lo[0] - rx, g.ox, g.inv_h, g.nx)), xb = nrm_uniform(bcell(hi[0] + rx, g.ox, g.inv_h, g.nx));
+    const int ya = nrm_uniform(bcell(lo[1] - rx, g.oy, g.inv_h, g.ny)), yb = nrm_uniform(bcell(hi[1] + rx, g.oy, g.inv_h, g.ny));
+    const int za = nrm_uniform(bcell(lo[2] - rx, g.oz, g.inv_h, g.nz)), zb = nrm_uniform(bcell(hi[2] + rx, g.oz, g.inv_h, g.nz));
+    const unsigned long long wave_in = static_cast<unsigned long long>(__popcll(__ballot(in)));
+    // the lanes of the group against stage[0 .. fill)
+    auto add = [&](const float4& pj) {
+      const double dx = static_cast<double>(pj.x) - qx, dy = static_cast<double>(pj.y) - qy,
+                   dz = static_cast<double>(pj.z) - qz;
+      s0 += dx;
+      s1 += dy;
+      s2 += dz;
+      sxx += dx * dx;
+      sxy += dx * dy;
+      sxz += dx * dz;
+      syy += dy * dy;
+      syz += dy * dz;
+      szz += dz * dz;
+      ++m;
+    };
+    auto scan = [&](int fill) {
+      __syncthreads();
+      if (in) {
+        // kNrmBatch LDS reads and tests in flight, then the hits in staged order
+        int j = 0;
+        for (; j + kNrmBatch <= fill; j += kNrmBatch) {
+          float4 pj[kNrmBatch];
+          bool hit[kNrmBatch];
+#pragma unroll
+          for (int b = 0; b < kNrmBatch; ++b) pj[b] = stage[j + b];
+#pragma unroll
+          for (int b = 0; b < kNrmBatch; ++b) hit[b] = dist2(q.x, q.y, q.z, pj[b]) < r2;
+#pragma unroll
+          for (int b = 0; b < kNrmBatch; ++b)
+            if (hit[b]) add(pj[b]);
+        }
+        for (; j < fill; ++j) {
+          const float4 pj = stage[j];
+          if (dist2(q.x, q.y, q.z, pj) < r2) add(pj);
+        }
+      }
+      tests += wave_in * static_cast<unsigned long long>(fill);
+      __syncthreads();
+    };
+    int fill = 0;
+    for (int z = za; z <= zb; ++z) {
+      for (int y = ya; y <= yb; ++y) {
+        const uint32_t* row = g.cell_start + (static_cast<size_t>(z) * g.ny + y) * g.nx;
+        uint32_t a = static_cast<uint32_t>(nrm_uniform(static_cast<int>(row[xa])));
+        const uint32_t b = static_cast<uint32_t>(nrm_uniform(static_cast<int>(row[xb + 1])));
+        while (a < b) {
+          const uint32_t take = min(b - a, static_cast<uint32_t>(kNrmStage - fill));
+          for (uint32_t i = static_cast<uint32_t>(t); i < take; i += kNrmThreads) stage[fill + i] = g.pts[a + i];
+          fill += static_cast<int>(take);
+          a += take;
+          if (fill == kNrmStage) {
+            scan(fill);
+            fill = 0;
+          }
+        }
+      }
+    }
+    if (fill) scan(fill);
+    cur += members;
+  }
+  if (valid) {
+    const float qnan = __uint_as_float(0x7fc00000u);
+    float4 o = make_float4(qnan, qnan, qnan, qnan);
+    if (m >= 3) {
+      const double md = static_cast<double>(m);
+      const double mu0 = s0 / md, mu1 = s1 / md, mu2 = s2 / md;
+      double a[3][3], v[3][3];
+      a[0][0] = sxx / md - mu0 * mu0;
+      a[0][1] = a[1][0] = sxy / md - mu0 * mu1;
+      a[0][2] = a[2][0] = sxz / md - mu0 * mu2;
+      a[1][1] = syy / md - mu1 * mu1;
+      a[1][2] = a[2][1] = syz / md - mu1 * mu2;
+      a[2][2] = szz / md - mu2 * mu2;
+      const double trace = (a[0][0] + a[1][1]) + a[2][2];
+      jacobi3(a, v);
+      // the smallest eigenvalue (the first of equal ones) and its column of v
+      int k = 0;
+      if (a[1][1] < a[0][0]) k = 1;
+      if (a[2][2] < sel3(k, a[0][0], a[1][1], a[2][2])) k = 2;
+      const double lam = sel3(k, a[0][0], a[1][1], a[2][2]);
+      double n0 = sel3(k, v[0][0], v[0][1], v[0][2]), n1 = sel3(k, v[1][0], v[1][1], v[1][2]),
+             n2 = sel3(k, v[2][0], v[2][1], v[2][2]);
+      const double len = sqrt((n0 * n0 + n1 * n1) + n2 * n2);
+      n0 /= len;
+      n1 /= len;
+      n2 /= len;
+      o.x = static_cast<float>(n0);
+      o.y = static_cast<float>(n1);
+      o.z = static_cast<float>(n2);
+      o.w = static_cast<float>(trace == 0.0 ? 0.0 : fabs(lam / trace));
+      // flipNormalTowardsViewpoint, decided on the rounded components that are returned
+      const double wx = static_cast<double>(vx) - qx, wy = static_cast<double>(vy) - qy, wz = static_cast<double>(vz) - qz;
+      double dot = wx * static_cast<double>(o.x);
+      dot = dot + wy * static_cast<double>(o.y);
+      dot = dot + wz * static_cast<double>(o.z);
+      if (dot < 0.0) {
+        o.x = -o.x;
+        o.y = -o.y;
+        o.z = -o.z;
+      }
+    }
+    const uint32_t oi = __float_as_uint(q.w);
+    out_orig[oi] = o;
+    count_orig[oi] = m;
+  }
+  if (lane == 0 && tests) atomicAdd(pair_tests, tests);
+}
+
 __global__ __launch_bounds__(256) void reduce_finish_kernel(const double* __restrict__ partial,
                                                             int nb, double* __restrict__ out) {
   double acc[kRedVals];
@@ -4146,6 +4345,15 @@ hipError_t launch_radius_keep(const GridView& g, size_t n, float r2, int need, u
   return hipGetLastError();
 }
 
+hipError_t launch_normals_tile(const GridView& g, size_t n, float r2, const float vp[3], float4* out, int* count,
+                               unsigned long long* pair_tests, hipStream_t s) {
+  if (!n) return hipSuccess;
+  const size_t nb = (n + kNrmThreads - 1) / kNrmThreads;
+  normals_tile_kernel<<<static_cast<unsigned int>(nb), kNrmThreads, 0, s>>>(g, n, r2, vp[0], vp[1], vp[2], out, count,
+                                                                          pair_tests);
+  return hipGetLastError();
+}
+
 hipError_t launch_reduce_finish(const double* partial, int nb, double* out, hipStream_t s) {
   reduce_finish_kernel<<<1, kRedThreads, 0, s>>>(partial, nb, out);
   return hipGetLastError();
@@ -4548,6 +4756,7 @@ hipError_t preload_kernels(void* pinned, size_t pinned_bytes, hipStream_t s) {
       reinterpret_cast<const void*>(&cc_link_kernel),
       reinterpret_cast<const void*>(&cc_root_kernel),
       reinterpret_cast<const void*>(&cc_emit_kernel),
+      reinterpret_cast<const void*>(&normals_tile_kernel),
   };
   for (const void* f : fns) {
     hipFuncAttributes attr;

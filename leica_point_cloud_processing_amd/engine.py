@@ -247,6 +247,23 @@ class GICPEngine:
                                                   int(min_neighbors), keep.ctypes.data), "radius_filter")
         return keep.astype(bool)
 
+    def estimate_normals(self, cloud, radius: float, viewpoint=None):
+        """pcl::NormalEstimation with a radius search (Utils::getNormals): (normals float32[n, 3],
+        curvature float32[n], n_neighbors int32[n], info).  A non-finite record or one with fewer than
+        3 radius neighbours (itself included) has a NaN normal and curvature; `viewpoint` None is
+        PCL's default (0, 0, 0)."""
+        _keep, ptr, n, stride = self._cloud_arg(cloud)
+        normals = np.zeros((max(n, 1), 3), np.float32)
+        curvature = np.zeros(max(n, 1), np.float32)
+        count = np.zeros(max(n, 1), np.int32)
+        vp = None if viewpoint is None else np.ascontiguousarray(viewpoint, np.float32).reshape(3)
+        ni = _lib.MgicpNormalsInfo()
+        self._check(self._lib.mgicp_estimate_normals(
+            self._h, ctypes.c_void_p(ptr), n, stride, float(radius), _fp(vp) if vp is not None else None,
+            normals.ctypes.data, 12, curvature.ctypes.data, count.ctypes.data, ctypes.byref(ni)), "estimate_normals")
+        info = {f: getattr(ni, f) for f, _ in ni._fields_}
+        return normals[:n], curvature[:n], count[:n], info
+
     # -- FOD-side callers (SURVEY.md 8f rows 2 and 4) ------------------------------------------
     def segment_differences(self, cloud_in, cloud_sub, sqr_threshold: float, T=None):
         """pcl::SegmentDifferences (Filter::removeFromCloud): bool keep mask over cloud_in (after T)

@@ -32,6 +32,22 @@ def is_valid_transform(T) -> bool:
     return not bool(np.isnan(np.asarray(T, dtype=np.float32)).any())
 
 
+def getNormals(cloud, normal_radius: float, engine: GICPEngine | None = None):
+    """Utils::getNormals (src/Utils.cpp:27-44): pcl::NormalEstimation with a radius search and the
+    default viewpoint.  Returns (success, normals): `normals` is float32 [n, 4], a pcl::Normal's
+    normal_x, normal_y, normal_z and curvature per record (NaN where PCL gives a NaN normal);
+    `success` is the reference's len(normals) == len(cloud)."""
+    log.info("Computing normals with radius: %f", normal_radius)
+    if engine is None:
+        from .filter import _engine
+
+        engine = _engine()
+    n, curvature, _count, _info = engine.estimate_normals(cloud, normal_radius)
+    normals = np.concatenate([n, curvature[:, None]], axis=1).astype(np.float32)
+    size = cloud.size() if isinstance(cloud, PointCloudRGB) else len(np.asarray(cloud).reshape(-1, 3))
+    return len(normals) == size, normals
+
+
 def matmul4f(a, b) -> np.ndarray:
     """Eigen Matrix4f * Matrix4f (column packets): ((a0 b0j + a1 b1j) + a2 b2j) + a3 b3j, float32."""
     a = np.asarray(a, dtype=np.float32)

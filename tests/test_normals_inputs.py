@@ -1,0 +1,134 @@
+"""CPU checks of the radius-normal cases (tests/normals_cases.py): every cloud is what it claims to be,
+few records are excluded from the direction and sign comparisons, and the bounds the GPU tests assert
+hold for a NumPy model of the arithmetic mgicp_estimate_normals is specified to use -- with room to
+PCL's float arithmetic on the other side.  Also: the adapter's Utils::getNormals compiles."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import normals_cases as nc
+from conftest import ROOT
+
+
+@pytest.mark.parametrize("name", nc.DIRECTION_CASES)
+def test_few_records_are_excluded(name):
+    """At most 1 % of a case's non-NaN records have a relative eigen-gap below GAP_MIN (no stable normal
+    in any arithmetic) and at most 1 % a view direction within COS_MIN of the tangent plane."""
+    xyz, _radius = nc.case(name)
+    ref = nc.case_reference(name)
+    has = ref.has
+    assert has.sum() > 0
+    low_gap = has & ~(ref.gap_rel >= nc.GAP_MIN)
+    print(name, "records", len(xyz), "with a normal", int(has.sum()), "gap below", nc.GAP_MIN, int(low_gap.sum()))
+    assert low_gap.sum() <= 0.01 * has.sum()
+    for vp in ((0.0, 0.0, 0.0),) + ((nc.VIEWPOINT,) if name == "part" else ()):
+        _sign, cos = nc.orientation(xyz, ref, vp)
+        grazing = has & ~(cos >= nc.COS_MIN)
+        print(name, "viewpoint", vp, "grazing", int(grazing.sum()))
+        assert grazing.sum() <= 0.01 * has.sum()
+
+
+@pytest.mark.parametrize("name", nc.DIRECTION_CASES)
+def test_model_meets_the_bounds(name):
+    """The specified arithmetic (fp64 raw moments of the differences) in NumPy: its normals are within
+    DIR_BOUND / gap_rel of the truth and its worst angle is below the MEDIAN angle of PCL's float
+    arithmetic on the same records; its curvature is within CURV_BOUND less the float rounding of the
+    output (2^-26 for a value of at most 1/3)."""
+    ref = nc.case_reference(name)
+    sel = ref.has & (ref.gap_rel >= nc.GAP_MIN)
+    worst = float(ref.model_angle[sel].max())
+    pcl_median = float(np.median(ref.pcl_angle[sel]))
+    print(name, "model worst angle", worst, "pcl median", pcl_median, "pcl max", float(ref.pcl_angle[sel].max()))
+    assert (ref.model_angle[sel] <= nc.DIR_BOUND / ref.gap_rel[sel] - 2.0 ** -24 * np.sqrt(3.0)).all()
+    assert worst <= pcl_median
+    assert np.abs(ref.model_curvature[ref.has] - ref.curvature[ref.has]).max() <= nc.CURV_BOUND - 2.0 ** -26
+
+
+def test_case_shapes():
+    """Each cloud reaches the part of the kernel it is there for."""
+    for name in nc.DIRECTION_CASES:
+        assert len(nc.case(name)[0]) <= 6000, name
+    cube, part, small = nc.case_reference("cube"), nc.case_reference("part"), nc.case_reference("part_small")
+    xyz, _ = nc.case("cube")
+    assert cube.has.all() and cube.count.min() >= 200 and cube.count.max() <= 500
+    assert (xyz.min(0) < 0).all() and (xyz.max(0) > 0).all()  # the default viewpoint lies inside
+    assert part.has.all() and 30 <= part.count.min() and part.count.max() <= 320
+    assert 0 < (~small.has).sum() < 0.1 * len(small.has) and small.count.max() <= 40
+    # clump: one cell with more points than a block has lanes, a neighbourhood past one staging chunk
+    xyz, radius = nc.case("clump")
+    h, most, _dims = nc.grid_facts(xyz, radius)
+    assert h == radius and most > nc.BLOCK_LANES and most > nc.STAGE_POINTS
+    assert nc.case_reference("clump").count.max() > nc.STAGE_POINTS
+    # huge radius: one cell, every point neighbours every point
+    xyz, radius = nc.case("huge_radius")
+    h, most, dims = nc.grid_facts(xyz, radius)
+    assert dims == [1, 1, 1] and most == len(xyz) == 777 and len(xyz) % 64
+    assert (nc.case_reference("huge_radius").count == 777).all()
+    assert radius > np.linalg.norm(xyz.max(0) - xyz.min(0))
+    # tiny radius: the cell edge is grown past the radius; most records have no normal
+    xyz, radius = nc.case("tiny_radius")
+    h, _most, dims = nc.grid_facts(xyz, radius)
+    ref = nc.case_reference("tiny_radius")
+    assert h > 5 * radius and max(dims) == 1 << 20
+    assert ref.has.sum() == 30 and (~ref.has).sum() == 600
+    # non-finite records: present, and without a normal
+    xyz, _ = nc.case("nonfinite")
+    bad = ~np.isfinite(xyz).all(1)
+    ref = nc.case_reference("nonfinite")
+    assert bad.sum() == 50 and np.isnan(xyz).any() and np.isposinf(xyz).any() and np.isneginf(xyz).any()
+    assert not ref.has[bad].any() and (ref.count[bad] == 0).all() and ref.has[~bad].sum() > 2000
+
+
+def test_degenerate_and_edge_clouds():
+    xyz, radius, rows = nc.degenerate()
+    ref = nc.reference(xyz, radius)
+    assert ref.has[rows].all()
+    # no plane: the two smallest eigenvalues of the centred covariance vanish against the largest, or all do
+    _fin, I, J = nc.neighbour_pairs(xyz, radius)
+    for i in rows:
+        nb = xyz[J[I == i]].astype(np.float64)
+        w = np.linalg.eigvalsh(np.cov(nb.T, bias=True))
+        assert w[1] <= 1e-9 * max(w[2], 1e-30) or w[2] == 0, (i, w)
+    edge = nc.edge_clouds()
+    assert nc.r2_of(edge["radius_zero"][1]) == 0
+    r2 = nc.r2_of(edge["denormal_r2"][1])
+    assert 0 < r2 < np.float32(1.17549435e-38)
+    cnt = nc.reference(*edge["denormal_r2"]).count
+    assert sorted(np.unique(cnt)) == [1, 2, 3] and (cnt[:3] == 3).all() and (cnt[3:6] == 2).all()
+    assert [len(edge[k][0]) for k in ("n0", "n1", "n2_near", "n2_far")] == [0, 1, 2, 2]
+    assert list(nc.reference(*edge["n2_near"]).count) == [2, 2] and list(nc.reference(*edge["n2_far"]).count) == [1, 1]
+
+
+def test_normals_adapter_compiles_against_standins():
+    """adapter/Utils_mi355x.cpp passes g++ -std=c++14 -Wall -Wextra -Werror against the stand-ins of
+    tests/adapter_standins_normals and links to libmgicp.so through product symbols only."""
+    from leica_point_cloud_processing_amd import _lib
+
+    r = subprocess.run(["make", "-s", "-C", ROOT, "normals-replay"], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    exe = os.path.join(ROOT, "adapter", "build", "replay_test_normals")
+    assert os.path.exists(exe)
+    nm = subprocess.run(["nm", "-C", exe], capture_output=True, text=True).stdout
+    assert "Utils::getNormals" in nm
+    needed = {line.split()[-1] for line in subprocess.run(["nm", "-u", exe], capture_output=True, text=True).stdout.splitlines()
+              if line.split() and line.split()[-1].startswith("mgicp_")}
+    assert "mgicp_estimate_normals" in needed
+    assert needed <= set(_lib.header_symbols(_lib.HEADER_PATH)), sorted(needed)
+
+
+def test_python_binding_matches_header():
+    """mgicp_normals_info: the ctypes mirror has the header's fields in the header's order, all double."""
+    import ctypes
+    import re
+
+    from leica_point_cloud_processing_amd import _lib
+
+    text = open(_lib.HEADER_PATH).read()
+    body = re.search(r"typedef struct \{([^}]*)\}\s*mgicp_normals_info;", text).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    fields = re.findall(r"\b(double|int)\s+(\w+)\s*;", body)
+    assert [(n, {"double": ctypes.c_double, "int": ctypes.c_int}[t]) for t, n in fields] == list(_lib.MgicpNormalsInfo._fields_)
+    assert "mgicp_estimate_normals" in _lib._SIGNATURES
+    assert "mgicp_estimate_normals" in _lib.header_symbols(_lib.HEADER_PATH)
