@@ -12,7 +12,7 @@ LDMAP := -Wl,--version-script=$(MAP)
 # -ffp-contract=off: no FMA contraction, so fp32/fp64 expressions round like PCL's SSE2 Eigen
 HIPFLAGS := -O3 -std=c++17 --offload-arch=$(ARCH) -fPIC -ffp-contract=off -Wall -Wno-unused-result
 
-all: $(LIB) oracle adapter-example adapter-replay fod-replay normals-replay
+all: $(LIB) oracle adapter-example adapter-replay fod-replay normals-replay boundary-replay
 
 OBJDIR := $(PKG)/csrc/build
 OBJS  := $(OBJDIR)/mgicp_kernels.o $(OBJDIR)/mgicp_engine.o $(OBJDIR)/mgicp_clouds.o $(OBJDIR)/mgicp_pass.o \
@@ -81,6 +81,22 @@ $(NRMREPLAY): adapter/Utils_mi355x.cpp include/mi355x_gicp.h $(wildcard $(STANDI
 
 normals-replay: $(NRMREPLAY)
 
+# adapter/InitialAlignment_mi355x.cpp (InitialAlignment::obtainBoundaryKeypoints) compiled the same way: the
+# InitialAlignment.h of tests/adapter_standins_boundary in front (the class with that private member), then
+# the Utils.h with pcl::Normal, linked with a driver that calls it on a cloud file and a normals file
+# (test infrastructure)
+STANDIN_BND := tests/adapter_standins_boundary
+BNDREPLAY   := adapter/build/replay_test_boundary
+$(BNDREPLAY): adapter/InitialAlignment_mi355x.cpp include/mi355x_gicp.h $(wildcard $(STANDIN)/*.h) \
+              $(wildcard $(STANDIN_NRM)/*.h) $(wildcard $(STANDIN_BND)/*.h) $(STANDIN)/Utils_standin.cpp \
+              $(STANDIN_BND)/replay_test_boundary.cpp $(LIB)
+	mkdir -p adapter/build
+	g++ -O2 -std=c++14 -Wall -Wextra -Werror -I$(STANDIN_BND) -I$(STANDIN_NRM) -I$(STANDIN) -Iadapter -Iinclude -o $@ \
+	    adapter/InitialAlignment_mi355x.cpp $(STANDIN)/Utils_standin.cpp $(STANDIN_BND)/replay_test_boundary.cpp \
+	    -L$(PKG) -lmgicp -Wl,-rpath,'$$ORIGIN/../../$(PKG)'
+
+boundary-replay: $(BNDREPLAY)
+
 oracle:
 	$(MAKE) -C oracle
 
@@ -88,4 +104,4 @@ clean:
 	rm -f $(LIB) $(PKG)/libmgicp_*.so $(OBJS)
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle clean adapter-example adapter-replay fod-replay normals-replay variant
+.PHONY: all oracle clean adapter-example adapter-replay fod-replay normals-replay boundary-replay variant

@@ -173,6 +173,51 @@ int mgicp_estimate_normals(mgicp_ctx* ctx, const float* xyz, size_t n, size_t st
                            int* n_neighbors /* may be NULL, packed n */,
                            mgicp_normals_info* info /* may be NULL */);
 
+/* InitialAlignment::obtainBoundaryKeypoints (src/InitialAlignment.cpp:426-456; the BOUNDARY and NORMALS
+ * methods call it on both clouds after getNormals): pcl::BoundaryEstimation<PointXYZRGB, Normal, Boundary>
+ * with setKSearch(30) and setAngleThreshold(1.047f); PCL 1.8.1 computeFeature / isBoundaryPoint /
+ * getCoordinateSystemOnPlane restated [PCL].
+ * Neighbour set of record i: its k nearest FINITE records, itself included, by FLANN's float
+ * ((dx^2) + dy^2) + dz^2; order and ties at the k-th distance go by (d2, original record index) -- the
+ * engine's rule; FLANN's choice among equal distances depends on its tree and is not reproduced.  With
+ * fewer than k finite records every finite record is in the set.  nn_indices[i * k ..] holds the set as
+ * original record indices in that order, padded with -1; a non-finite record gets all -1.
+ * Never a boundary point (max_gap = NaN, boundary = 0): a non-finite record; a record whose normal has a
+ * non-finite component (deliberate: in PCL the NaN angles go through std::sort and the answer is "false"
+ * in practice); a set of fewer than 3 records; a set in which every member has
+ * delta = p_j - q_i = (0, 0, 0).  (A finite normal that still makes an angle NaN -- zero length, or
+ * squares that overflow -- is treated like a non-finite one.)
+ * Otherwise, all in float without FMA contraction: v = Eigen's generic unitOrthogonal of (n_x, n_y, n_z, 0)
+ * (maxi = the first index of the largest |component|, sndi = maxi == 0 ? 1 : 0,
+ * inv = 1 / sqrt(n[sndi]^2 + n[maxi]^2), v[maxi] = -n[sndi] inv, v[sndi] = n[maxi] inv, the rest 0),
+ * u = n x v; for each member with delta != 0 the angle atan2f(v . delta, u . delta), dots summed as
+ * (x + y) + z; the angles sorted ascending; max_dif starts at FLT_MIN and takes every consecutive
+ * difference and the wrap (2 float(pi) - last) + first; max_gap[i] = max_dif and
+ * boundary[i] = max_gap[i] > (float)angle_threshold.  PCL's SIMD dot order and its libm atan2f are not
+ * pinned: the decision does not depend on the choice of (u, v) in exact arithmetic, so they matter at
+ * rounding level only (DESIGN.md "Boundary estimation").
+ * normals: x, y, z at byte offsets 0/4/8 of records of normal_stride_bytes (>= 12, a multiple of 4; 32
+ * for pcl::Normal).  k outside [1, 32], a NaN threshold, a bad pointer or stride: MGICP_E_INVALID;
+ * n = 0: OK; k < 3 is legal and flags nothing.  The same bits in every output on every call.
+ * Uses the helper cloud slot: a set source / target and their cached state stay as they are.
+ * Single rank: with a communicator attached it runs locally, without a collective. */
+typedef struct {
+    double n_finite;     /* finite records (the searched tree) */
+    double n_boundary;   /* records flagged 1 */
+    double n_undecided;  /* finite records that got max_gap = NaN (rules above) */
+    double pair_tests;   /* point-pair distance evaluations the device made */
+    double ms_grid;      /* host call -> grid of the finite records built (uploads included) */
+    double ms_device;    /* first launch -> stream synchronise after the last */
+    double ms_total;     /* host call -> outputs written */
+} mgicp_boundary_info;
+int mgicp_boundary_points(mgicp_ctx* ctx, const float* xyz, size_t n, size_t stride_bytes,
+                          const float* normals, size_t normal_stride_bytes,
+                          int k, double angle_threshold,
+                          unsigned char* boundary /* n, 0/1 */,
+                          float* max_gap /* may be NULL, packed n */,
+                          int* nn_indices /* may be NULL, n * k */,
+                          mgicp_boundary_info* info /* may be NULL */);
+
 /* ---- the FOD-side callers either side of the GICP path ----
  * pcl::SegmentDifferences<PointXYZRGB>::segment as called by Filter::removeFromCloud
  * (src/Filter.cpp:176-189) on the cloud the FSM just transformed with

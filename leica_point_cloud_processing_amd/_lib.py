@@ -79,6 +79,18 @@ class MgicpNormalsInfo(ctypes.Structure):
     ]
 
 
+class MgicpBoundaryInfo(ctypes.Structure):
+    _fields_ = [
+        ("n_finite", ctypes.c_double),
+        ("n_boundary", ctypes.c_double),
+        ("n_undecided", ctypes.c_double),
+        ("pair_tests", ctypes.c_double),
+        ("ms_grid", ctypes.c_double),
+        ("ms_device", ctypes.c_double),
+        ("ms_total", ctypes.c_double),
+    ]
+
+
 class MgicpError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"mgicp error {code}: {msg}")
@@ -110,6 +122,8 @@ _SIGNATURES = {
     "mgicp_radius_filter": (ctypes.c_int, [_P, _P, _SZ, _SZ, ctypes.c_double, ctypes.c_int, _P]),
     "mgicp_estimate_normals": (ctypes.c_int, [_P, _P, _SZ, _SZ, ctypes.c_double, _FP, _P, _SZ, _P, _P,
                                                ctypes.POINTER(MgicpNormalsInfo)]),
+    "mgicp_boundary_points": (ctypes.c_int, [_P, _P, _SZ, _SZ, _P, _SZ, ctypes.c_int, ctypes.c_double, _P, _P, _P,
+                                              ctypes.POINTER(MgicpBoundaryInfo)]),
     "mgicp_segment_differences": (ctypes.c_int, [_P, _FP, _P, _SZ, _SZ, _P, _SZ, _SZ, ctypes.c_double, _P,
                                                   ctypes.POINTER(_SZ)]),
     "mgicp_voxel_grid": (ctypes.c_int, [_P, _P, _SZ, _SZ, ctypes.c_int, _DP, ctypes.c_int, _P, _SZ,

@@ -1,6 +1,6 @@
 // mgicp_fod.hip -- the product calls beside the alignment (include/mi355x_gicp.h): point transforms,
-// cloud resolution, the radius filter, radius normals, segment differences, Euclidean clustering and the
-// voxel grid.
+// cloud resolution, the radius filter, radius normals, boundary points, segment differences, Euclidean
+// clustering and the voxel grid.
 #pragma clang fp contract(off)
 
 #include <hip/hip_runtime.h>
@@ -201,6 +201,75 @@ int mgicp_estimate_normals(mgicp_ctx* ctx, const float* xyz, size_t n, size_t st
   inf.pair_tests = static_cast<double>(ntests);
   inf.ms_grid = t1 - t0;
   inf.ms_device = t3 - t2;
+  inf.ms_total = now_ms() - t0;
+  if (info) *info = inf;
+  return MGICP_OK;
+}
+
+int mgicp_boundary_points(mgicp_ctx* ctx, const float* xyz, size_t n, size_t stride, const float* normals,
+                          size_t normal_stride, int k, double angle_threshold, unsigned char* boundary, float* max_gap,
+                          int* nn_indices, mgicp_boundary_info* info) {
+  if (!ctx || k < 1 || k > kMaxK || angle_threshold != angle_threshold || (n && (!xyz || !normals || !boundary)) ||
+      stride < 12 || (stride % 4) || normal_stride < 12 || (normal_stride % 4))
+    return MGICP_E_INVALID;
+  HIPCK(hipSetDevice(ctx->device));
+  const double t0 = now_ms();
+  mgicp_boundary_info inf{};
+  if (info) *info = inf;
+  if (n == 0) return MGICP_OK;
+  // the tree holds the finite records only; the grid is sized by occupancy like a set cloud's
+  int rc = aux_grid(ctx, xyz, n, stride);
+  if (rc) return rc;
+  const size_t nf = ctx->aux.n;
+  hipStream_t s = ctx->stream;
+  const size_t nk = n * static_cast<size_t>(k);
+  std::vector<float> hn(3 * n);
+  const unsigned char* nbase = reinterpret_cast<const unsigned char*>(normals);
+  for (size_t i = 0; i < n; ++i) std::memcpy(&hn[3 * i], nbase + i * normal_stride, 12);
+  ScopedBuf<float> d_nrm, d_gap;
+  ScopedBuf<unsigned char> d_flag;
+  ScopedBuf<int> d_nn;
+  ScopedBuf<uint32_t> d_fb;
+  ScopedBuf<unsigned int> d_cnt;
+  HIPCK(d_nrm.reserve(3 * n));
+  HIPCK(d_gap.reserve(n));
+  HIPCK(d_flag.reserve(n));
+  HIPCK(d_fb.reserve(std::max<size_t>(nf, 1)));
+  HIPCK(d_cnt.reserve(1));
+  if (nn_indices) HIPCK(d_nn.reserve(nk));
+  HIPCK(ctx->cc_tests.reserve(1));
+  HIPCK(hipMemcpyAsync(d_nrm.p, hn.data(), 3 * n * sizeof(float), hipMemcpyHostToDevice, s));
+  if ((rc = sync(ctx))) return rc;
+  const double t1 = now_ms();
+  // records that are never boundary points keep these: flag 0, gap a quiet NaN, every index -1
+  HIPCK(hipMemsetAsync(d_flag.p, 0, n, s));
+  HIPCK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_gap.p), 0x7fc00000, n, s));
+  if (nn_indices) HIPCK(hipMemsetAsync(d_nn.p, 0xff, nk * sizeof(int), s));
+  HIPCK(hipMemsetAsync(d_cnt.p, 0, sizeof(unsigned int), s));
+  HIPCK(hipMemsetAsync(ctx->cc_tests.p, 0, sizeof(unsigned long long), s));
+  HIPCK(launch_boundary(ctx->aux.view, nf, d_nrm.p, k, static_cast<float>(angle_threshold), d_flag.p, d_gap.p,
+                        nn_indices ? d_nn.p : nullptr, d_fb.p, d_cnt.p, ctx->cc_tests.p, s));
+  if ((rc = sync(ctx))) return rc;
+  const double t2 = now_ms();
+  std::vector<float> hg(max_gap ? 0 : n);
+  float* gp = max_gap ? max_gap : hg.data();
+  unsigned long long ntests = 0;
+  HIPCK(hipMemcpyAsync(boundary, d_flag.p, n, hipMemcpyDeviceToHost, s));
+  HIPCK(hipMemcpyAsync(gp, d_gap.p, n * sizeof(float), hipMemcpyDeviceToHost, s));
+  if (nn_indices) HIPCK(hipMemcpyAsync(nn_indices, d_nn.p, nk * sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCK(hipMemcpyAsync(&ntests, ctx->cc_tests.p, sizeof(ntests), hipMemcpyDeviceToHost, s));
+  if ((rc = sync(ctx))) return rc;
+  size_t n_boundary = 0, n_nan = 0;
+  for (size_t i = 0; i < n; ++i) {
+    n_boundary += boundary[i] != 0;
+    n_nan += gp[i] != gp[i];
+  }
+  inf.n_finite = static_cast<double>(nf);
+  inf.n_boundary = static_cast<double>(n_boundary);
+  inf.n_undecided = static_cast<double>(n_nan - (n - nf));  // every non-finite record has a NaN gap
+  inf.pair_tests = static_cast<double>(ntests);
+  inf.ms_grid = t1 - t0;
+  inf.ms_device = t2 - t1;
   inf.ms_total = now_ms() - t0;
   if (info) *info = inf;
   return MGICP_OK;

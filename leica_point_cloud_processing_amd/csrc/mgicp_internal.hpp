@@ -341,6 +341,17 @@ hipError_t launch_cc_labels(const GridView& g, const uint32_t* perm, size_t n, u
 hipError_t launch_normals_tile(const GridView& g, size_t n, float r2, const float vp[3], float4* out, int* count,
                                unsigned long long* pair_tests, hipStream_t s);
 
+// BoundaryEstimation with a k-search (InitialAlignment::obtainBoundaryKeypoints): for every grid point, over
+// its k nearest grid points in (float d2, original index) order (itself included), the largest cyclic gap of
+// the tangent-plane angles in gap[original index] and gap > thr in flag[original index]; records that are
+// never boundary points keep the caller's presets (0 / NaN).  normals: 3 floats per original record.
+// nn (nullable, preset to -1): k original indices per original record, in that order.  fb / fb_count
+// (n entries / one zeroed counter): the queries the per-lane kernel hands to the wave-per-query one.
+// *pair_tests (zeroed by the caller) += distance evaluations.  k in [1, 32].
+hipError_t launch_boundary(const GridView& g, size_t n, const float* normals, int k, float thr, uint8_t* flag,
+                           float* gap, int* nn, uint32_t* fb, unsigned int* fb_count,
+                           unsigned long long* pair_tests, hipStream_t s);
+
 #if defined(MGICP_CORR_PHASES) && MGICP_CORR_PHASES
 hipError_t corr_phase_take(unsigned long long out[24]);  // diagnostic builds: read and reset
 #endif

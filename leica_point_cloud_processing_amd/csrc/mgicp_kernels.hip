@@ -976,6 +976,112 @@ struct WaveKnnLane {
   }
 };
 
+// The wave's ring walk for one query (every lane of the wave calls it with the same arguments): on return
+// the k nearest keys of the query are spread over the lanes' lists.  kCapped: the walk gives up before ring
+// `ring_cap + 1` and returns false (the lists are then incomplete); *tests += the distance evaluations.
+template <int K, bool kCapped>
+__device__ __forceinline__ bool wave_ring_search(const GridView& g, float qx, float qy, float qz, int k, int lane,
+                                                 WaveKnnLane<K>& L, int ring_cap, unsigned long long* tests) {
+  const int cx = qcell(qx, g.ox, g.inv_h), cy = qcell(qy, g.oy, g.inv_h), cz = qcell(qz, g.oz, g.inv_h);
+  int rmin = max(max(dist_out(cx, g.nx), dist_out(cy, g.ny)), dist_out(cz, g.nz));
+  if (rmin == 0 && g.empty_dist)
+    rmin = g.empty_dist[static_cast<size_t>(cx) +
+                        static_cast<size_t>(g.nx) * (static_cast<size_t>(cy) + static_cast<size_t>(g.ny) * cz)];
+  for (int r = rmin; r < (1 << 22); ++r) {
+    if constexpr (kCapped) {
+      if (r > ring_cap) return false;
+    }
+    if (r > 0) {
+      const float Lb = fminf(fminf(axis_bound(qx, g.ox, g.h, cx, r - 1, g.nx), axis_bound(qy, g.oy, g.h, cy, r - 1, g.ny)),
+                             axis_bound(qz, g.oz, g.h, cz, r - 1, g.nz));
+      if (Lb == INFINITY) break;  // every cell visited
+      const float Ls = Lb * 0.99999f - g.slop;
+      int nb = Ls > 0.f ? L.below(Ls * Ls) : 0;
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) nb += __shfl_xor(nb, o, 64);
+      if (nb >= k) break;
+    }
+    // the wave's tightest upper bound of the k-th distance at the ring start
+    float wb = L.kth2();
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) wb = fminf(wb, __shfl_xor(wb, o, 64));
+    const int x0 = cx - r, x1 = cx + r, y0 = cy - r, y1 = cy + r, z0 = cz - r, z1 = cz + r;
+    const int xlo = max(x0, 0), xhi = min(x1, g.nx - 1);
+    const int ylo = max(y0, 0), yhi = min(y1, g.ny - 1);
+    const int zlo = max(z0, 0), zhi = min(z1, g.nz - 1);
+    if (xlo > xhi || ylo > yhi || zlo > zhi) continue;
+    const int ny_r = yhi - ylo + 1;
+    const int nrows = (zhi - zlo + 1) * ny_r;
+    // rows in batches of 64 (one per lane): each lane forms its row's candidate ranges (pruned against
+    // the wave's bound), then the batch's points are flattened over the wave -- lane l tests points l,
+    // l + 64, ... of the concatenated ranges -- so a row crossing a dense surface does not leave one lane
+    // to scan it while 63 wait (the hand-off's points: dense clusters, duplicates)
+    for (int t0 = 0; t0 < nrows; t0 += 64) {
+      uint32_t a1 = 0, b1 = 0, a2 = 0, b2 = 0;
+      const int t = t0 + lane;
+      float wbb = L.kth2();
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) wbb = fminf(wbb, __shfl_xor(wbb, o, 64));
+      const float w = fminf(wbb, wb) * 1.00001f;
+      if (t < nrows) {
+        const int z = zlo + t / ny_r, y = ylo + t % ny_r;
+        const bool zf = (z == z0) || (z == z1);
+        const float gz = cell_gap(qz, g.oz, g.h, z, g.slop);
+        const float gy = cell_gap(qy, g.oy, g.h, y, g.slop);
+        const float gyz = gy * gy + gz * gz;
+        if (gyz <= w) {
+          const uint32_t* row = g.cell_start + (static_cast<size_t>(z) * g.ny + y) * g.nx;
+          if (zf || y == y0 || y == y1) {
+            const float rx = sqrtf(w - gyz) + g.slop;
+            const int xa = max(xlo, qcell(qx - rx, g.ox, g.inv_h));
+            const int xb = min(xhi, qcell(qx + rx, g.ox, g.inv_h));
+            if (xa <= xb) { a1 = row[xa]; b1 = row[xb + 1]; }
+          } else {
+            if (x0 >= 0) {
+              const float gx = cell_gap(qx, g.ox, g.h, x0, g.slop);
+              if (gx * gx + gyz <= w) { a1 = row[x0]; b1 = row[x0 + 1]; }
+            }
+            if (x1 < g.nx) {
+              const float gx = cell_gap(qx, g.ox, g.h, x1, g.slop);
+              if (gx * gx + gyz <= w) { a2 = row[x1]; b2 = row[x1 + 1]; }
+            }
+          }
+        }
+      }
+      const uint32_t n1 = b1 - a1, cnt = n1 + (b2 - a2);
+      uint32_t inc = cnt;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t u = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += u;
+      }
+      const uint32_t off = inc - cnt;
+      const uint32_t tot = __builtin_amdgcn_readlane(inc, 63);
+      if constexpr (kCapped) *tests += tot;
+      for (uint32_t f0 = 0; f0 < tot; f0 += 64) {
+        const uint32_t f = f0 + static_cast<uint32_t>(lane);
+        // the owner: the last lane whose range starts at or before f (binary search over the offsets)
+        int lo = 0;
+#pragma unroll
+        for (int step = 32; step > 0; step >>= 1) {
+          const uint32_t om = __shfl(off, lo + step, 64);
+          if (lo + step < 64 && om <= f) lo += step;
+        }
+        const uint32_t o_off = __shfl(off, lo, 64), o_a1 = __shfl(a1, lo, 64), o_n1 = __shfl(n1, lo, 64);
+        const uint32_t o_a2 = __shfl(a2, lo, 64);
+        if (f < tot) {
+          const uint32_t i = f - o_off;
+          const uint32_t j = i < o_n1 ? o_a1 + i : o_a2 + (i - o_n1);
+          const float4 pt = g.pts[j];
+          const unsigned long long c = mkkey(dist2(qx, qy, qz, pt), pt.w);
+          if (c < L.key[K - 1]) L.insert(c, j);
+        }
+      }
+    }
+  }
+  return true;
+}
+
 // queries: list[i] (sorted positions of the cloud) for i < *count (device count) or n; one wave each,
 // grid-striding.  k <= K neighbours (K: the instantiation).
 template <int K>
@@ -991,99 +1097,7 @@ __global__ __launch_bounds__(256) void knn_wave_kernel(GridView g, double eps, c
     const float qx = q.x, qy = q.y, qz = q.z;
     WaveKnnLane<K> L;
     L.init();
-    const int cx = qcell(qx, g.ox, g.inv_h), cy = qcell(qy, g.oy, g.inv_h), cz = qcell(qz, g.oz, g.inv_h);
-    int rmin = max(max(dist_out(cx, g.nx), dist_out(cy, g.ny)), dist_out(cz, g.nz));
-    if (rmin == 0 && g.empty_dist)
-      rmin = g.empty_dist[static_cast<size_t>(cx) +
-                          static_cast<size_t>(g.nx) * (static_cast<size_t>(cy) + static_cast<size_t>(g.ny) * cz)];
-    for (int r = rmin; r < (1 << 22); ++r) {
-      if (r > 0) {
-        const float Lb = fminf(fminf(axis_bound(qx, g.ox, g.h, cx, r - 1, g.nx), axis_bound(qy, g.oy, g.h, cy, r - 1, g.ny)),
-                               axis_bound(qz, g.oz, g.h, cz, r - 1, g.nz));
-        if (Lb == INFINITY) break;  // every cell visited
-        const float Ls = Lb * 0.99999f - g.slop;
-        int nb = Ls > 0.f ? L.below(Ls * Ls) : 0;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) nb += __shfl_xor(nb, o, 64);
-        if (nb >= k) break;
-      }
-      // the wave's tightest upper bound of the k-th distance at the ring start
-      float wb = L.kth2();
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) wb = fminf(wb, __shfl_xor(wb, o, 64));
-      const int x0 = cx - r, x1 = cx + r, y0 = cy - r, y1 = cy + r, z0 = cz - r, z1 = cz + r;
-      const int xlo = max(x0, 0), xhi = min(x1, g.nx - 1);
-      const int ylo = max(y0, 0), yhi = min(y1, g.ny - 1);
-      const int zlo = max(z0, 0), zhi = min(z1, g.nz - 1);
-      if (xlo > xhi || ylo > yhi || zlo > zhi) continue;
-      const int ny_r = yhi - ylo + 1;
-      const int nrows = (zhi - zlo + 1) * ny_r;
-      // rows in batches of 64 (one per lane): each lane forms its row's candidate ranges (pruned against
-      // the wave's bound), then the batch's points are flattened over the wave -- lane l tests points l,
-      // l + 64, ... of the concatenated ranges -- so a row crossing a dense surface does not leave one lane
-      // to scan it while 63 wait (the hand-off's points: dense clusters, duplicates)
-      for (int t0 = 0; t0 < nrows; t0 += 64) {
-        uint32_t a1 = 0, b1 = 0, a2 = 0, b2 = 0;
-        const int t = t0 + lane;
-        float wbb = L.kth2();
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) wbb = fminf(wbb, __shfl_xor(wbb, o, 64));
-        const float w = fminf(wbb, wb) * 1.00001f;
-        if (t < nrows) {
-          const int z = zlo + t / ny_r, y = ylo + t % ny_r;
-          const bool zf = (z == z0) || (z == z1);
-          const float gz = cell_gap(qz, g.oz, g.h, z, g.slop);
-          const float gy = cell_gap(qy, g.oy, g.h, y, g.slop);
-          const float gyz = gy * gy + gz * gz;
-          if (gyz <= w) {
-            const uint32_t* row = g.cell_start + (static_cast<size_t>(z) * g.ny + y) * g.nx;
-            if (zf || y == y0 || y == y1) {
-              const float rx = sqrtf(w - gyz) + g.slop;
-              const int xa = max(xlo, qcell(qx - rx, g.ox, g.inv_h));
-              const int xb = min(xhi, qcell(qx + rx, g.ox, g.inv_h));
-              if (xa <= xb) { a1 = row[xa]; b1 = row[xb + 1]; }
-            } else {
-              if (x0 >= 0) {
-                const float gx = cell_gap(qx, g.ox, g.h, x0, g.slop);
-                if (gx * gx + gyz <= w) { a1 = row[x0]; b1 = row[x0 + 1]; }
-              }
-              if (x1 < g.nx) {
-                const float gx = cell_gap(qx, g.ox, g.h, x1, g.slop);
-                if (gx * gx + gyz <= w) { a2 = row[x1]; b2 = row[x1 + 1]; }
-              }
-            }
-          }
-        }
-        const uint32_t n1 = b1 - a1, cnt = n1 + (b2 - a2);
-        uint32_t inc = cnt;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-          const uint32_t u = __shfl_up(inc, o, 64);
-          if (lane >= o) inc += u;
-        }
-        const uint32_t off = inc - cnt;
-        const uint32_t tot = __builtin_amdgcn_readlane(inc, 63);
-        for (uint32_t f0 = 0; f0 < tot; f0 += 64) {
-          const uint32_t f = f0 + static_cast<uint32_t>(lane);
-          // the owner: the last lane whose range starts at or before f (binary search over the offsets)
-          int lo = 0;
-#pragma unroll
-          for (int step = 32; step > 0; step >>= 1) {
-            const uint32_t om = __shfl(off, lo + step, 64);
-            if (lo + step < 64 && om <= f) lo += step;
-          }
-          const uint32_t o_off = __shfl(off, lo, 64), o_a1 = __shfl(a1, lo, 64), o_n1 = __shfl(n1, lo, 64);
-          const uint32_t o_a2 = __shfl(a2, lo, 64);
-          if (f < tot) {
-            const uint32_t i = f - o_off;
-            const uint32_t j = i < o_n1 ? o_a1 + i : o_a2 + (i - o_n1);
-            const float4 pt = g.pts[j];
-            const unsigned long long c = mkkey(dist2(qx, qy, qz, pt), pt.w);
-            if (c < L.key[K - 1]) L.insert(c, j);
-          }
-        }
-      }
-    }
+    wave_ring_search<K, false>(g, qx, qy, qz, k, lane, L, 0, nullptr);
     // k-round merge in ascending key order; the moments in that order (cov_from_sorted's)
     double m0 = 0.0, m1 = 0.0, m2 = 0.0;
     double a[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
@@ -3649,6 +3663,329 @@ __global__ __launch_bounds__(kNrmThreads) void normals_tile_kernel(GridView g, s
   if (lane == 0 && tests) atomicAdd(pair_tests, tests);
 }
 
+// ------------------------------------------------------------------------------------
+// Boundary estimation (pcl::BoundaryEstimation with a k-search, as
+// InitialAlignment::obtainBoundaryKeypoints calls it) -- DESIGN.md "Boundary estimation".
+// ------------------------------------------------------------------------------------
+// One lane per query, queries in grid order.  boundary_kernel finds the exact k-th float d2 (tau) with
+// KthVisitor<32> (32 - k sentinel slots) while logging candidates in the lane's LDS log; the set is
+// then read off the log: every entry with d2 < tau, plus, of the entries with d2 == tau, those with the
+// lowest original indices until the set holds k -- the first k of the (d2, original index) order,
+// because every entry with d2 <= tau is in the log (thresholds only fall) and original indices are
+// distinct.  A call that wants the indices runs boundary_sorted_kernel instead, one lane per query with
+// KnnVisitor's sorted (d2, index) list.  Either stops a query after ring kBndRingCap (a record whose
+// neighbours lie that many cells away -- an outlier metres off the part -- would walk hundreds of empty
+// rings on one lane while 63 wait) and lists it, as boundary_kernel lists a lane whose log overflowed,
+// for the one hand-off launch: boundary_wave_kernel, a wave per query.  All three feed the members to
+// the same BndAngles, whose result depends on the set alone (the angles are sorted).
+constexpr int kBndK = 32;         // list slots: the bound of k
+constexpr int kBndCap = 60;       // log entries per lane (knn_log_cap's K + 28): 15 KiB of LDS per wave
+constexpr int kBndRingCap = 8;    // rings a lane walks before it leaves the query to the hand-off
+constexpr int kBndWaveRings = 48; // rings a wave walks before it scans the whole cloud instead
+
+struct BndKth : KthVisitor<kBndK> {
+  unsigned nt = 0;  // distance evaluations of this lane
+  __device__ __forceinline__ void range(const GridView& g, uint32_t a, uint32_t b) {
+    nt += b - a;
+    KthVisitor<kBndK>::range(g, a, b);
+  }
+};
+
+struct BndKnn : KnnVisitor<kBndK> {
+  static constexpr bool kRingCap = true;
+  int ring_cap = kBndRingCap;
+  bool gave_up = false;
+  unsigned nt = 0;
+  __device__ __forceinline__ void range(const GridView& g, uint32_t a, uint32_t b) {
+    nt += b - a;
+    KnnVisitor<kBndK>::range(g, a, b);
+  }
+};
+
+// The angle criterion of BoundaryEstimation::isBoundaryPoint [PCL] in float, no contraction: the
+// tangent frame of getCoordinateSystemOnPlane (Eigen's generic unitOrthogonal of (n, 0), u = n x v),
+// one atan2f per member with a non-zero difference, kept in an ascending register list by the med3
+// insertion network (statically indexed, padded with +inf), then the largest cyclic gap.
+struct BndAngles {
+  float qx, qy, qz;
+  float ux, uy, uz, vx, vy, vz;
+  float a[kBndK];
+  int cp;
+  bool bad;  // an angle was NaN (a normal of zero length or one whose squares overflow)
+
+  __device__ __forceinline__ void init(const float4& q, float n0, float n1, float n2) {
+    qx = q.x; qy = q.y; qz = q.z;
+    // maxi: the first index of the largest |component| of (n0, n1, n2, 0); sndi = maxi == 0 ? 1 : 0
+    int maxi = 0;
+    float m = fabsf(n0);
+    if (fabsf(n1) > m) { maxi = 1; m = fabsf(n1); }
+    if (fabsf(n2) > m) maxi = 2;
+    const float ns = maxi == 0 ? n1 : n0;                       // n[sndi]
+    const float nm = maxi == 0 ? n0 : (maxi == 1 ? n1 : n2);  // n[maxi]
+    const float inv = 1.f / sqrtf(ns * ns + nm * nm);
+    const float vm = -ns * inv, vs = nm * inv;  // v[maxi], v[sndi]
+    vx = maxi == 0 ? vm : vs;
+    vy = maxi == 0 ? vs : (maxi == 1 ? vm : 0.f);
+    vz = maxi == 2 ? vm : 0.f;
+    ux = n1 * vz - n2 * vy;
+    uy = n2 * vx - n0 * vz;
+    uz = n0 * vy - n1 * vx;
+    cp = 0;
+    bad = false;
+#pragma unroll
+    for (int j = 0; j < kBndK; ++j) a[j] = INFINITY;
+  }
+  __device__ __forceinline__ void add(const float4& p) {
+    const float dx = p.x - qx, dy = p.y - qy, dz = p.z - qz;
+    if (dx == 0.f && dy == 0.f && dz == 0.f) return;
+    float s = vx * dx;
+    s = s + vy * dy;
+    s = s + vz * dz;
+    float c = ux * dx;
+    c = c + uy * dy;
+    c = c + uz * dz;
+    const float ang = atan2f(s, c);
+    bad = bad || ang != ang;
+#pragma unroll
+    for (int j = kBndK - 1; j > 0; --j) a[j] = __builtin_amdgcn_fmed3f(a[j - 1], ang, a[j]);
+    a[0] = fminf(ang, a[0]);
+    ++cp;
+  }
+  // max_gap: NaN when no member had a non-zero difference
+  __device__ __forceinline__ float gap() const {
+    if (cp == 0 || bad) return __uint_as_float(0x7fc00000u);
+    float max_dif = 1.17549435e-38f, last = a[0];
+#pragma unroll
+    for (int j = 1; j < kBndK; ++j) {
+      if (j < cp) {
+        const float dif = a[j] - a[j - 1];
+        if (max_dif < dif) max_dif = dif;
+        last = a[j];
+      }
+    }
+    const float dif = (6.28318548f - last) + a[0];  // 2 * float(pi)
+    if (max_dif < dif) max_dif = dif;
+    return max_dif;
+  }
+};
+
+__device__ __forceinline__ bool bnd_finite3(float a, float b, float c) {
+  return fabsf(a) < INFINITY && fabsf(b) < INFINITY && fabsf(c) < INFINITY;
+}
+
+__device__ __forceinline__ void bnd_count(unsigned nt, unsigned long long* pair_tests) {
+  unsigned long long v = nt;  // every lane of the wave is here
+#pragma unroll
+  for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
+  if ((threadIdx.x & 63) == 0 && v) atomicAdd(pair_tests, v);
+}
+
+// flag / gap: one entry per original record, preset by the caller (0 / NaN); normals: 3 floats per
+// original record; fb / fb_count: the sorted positions left to boundary_sorted_kernel
+__global__ __launch_bounds__(64, 1) void boundary_kernel(GridView g, size_t n, const float* __restrict__ normals, int k,
+                                                         float thr, uint8_t* __restrict__ flag, float* __restrict__ gap,
+                                                         uint32_t* __restrict__ fb, unsigned int* __restrict__ fb_count,
+                                                         unsigned long long* __restrict__ pair_tests) {
+  __shared__ uint32_t s_pos[kBndCap * 64];
+  const size_t t = static_cast<size_t>(blockIdx.x) * 64 + threadIdx.x;
+  unsigned nt = 0;
+  if (t < n) {
+    const float4 q = g.pts[t];
+    const uint32_t oi = __float_as_uint(q.w);
+    const float n0 = normals[3 * static_cast<size_t>(oi)], n1 = normals[3 * static_cast<size_t>(oi) + 1],
+                n2 = normals[3 * static_cast<size_t>(oi) + 2];
+    if (bnd_finite3(n0, n1, n2)) {  // else: never a boundary point, the presets stay
+      BndKth vis;
+      vis.init(q.x, q.y, q.z, kBndK - k);
+      uint32_t* lp = s_pos + threadIdx.x;
+      vis.lpos = lp;
+      vis.pts = g.pts;
+      vis.cap = kBndCap;
+      vis.ring_cap = kBndRingCap;
+      ring_search(g, q.x, q.y, q.z, vis);
+      nt = vis.nt;
+      if (vis.gave_up || vis.cnt > kBndCap) {
+        fb[atomicAdd(fb_count, 1u)] = static_cast<uint32_t>(t);
+      } else {
+        const float tau = vis.key[kBndK - 1];  // the k-th d2; +inf with fewer than k points
+        BndAngles ang;
+        ang.init(q, n0, n1, n2);
+        // entries below tau are members; ties at tau are counted, the first is kept
+        int nlt = 0, neq = 0;
+        uint32_t tie0 = 0;
+        for (int i0 = 0; i0 < vis.cnt; i0 += kLogBatch) {
+          uint32_t j[kLogBatch];
+          float4 pb[kLogBatch];
+#pragma unroll
+          for (int u = 0; u < kLogBatch; ++u) j[u] = lp[min(i0 + u, vis.cnt - 1) * 64];
+#pragma unroll
+          for (int u = 0; u < kLogBatch; ++u) pb[u] = g.pts[j[u]];
+#pragma unroll
+          for (int u = 0; u < kLogBatch; ++u) {
+            if (i0 + u >= vis.cnt) continue;
+            const float d = dist2(q.x, q.y, q.z, pb[u]);
+            if (d < tau) {
+              ++nlt;
+              ang.add(pb[u]);
+            } else if (d == tau) {
+              if (neq == 0) tie0 = j[u];
+              ++neq;
+            }
+          }
+        }
+        nt += static_cast<unsigned>(vis.cnt);
+        const int need = k - nlt;  // >= neq with fewer than k points, >= 1 otherwise
+        const int take = min(neq, need);
+        if (neq == 1) {
+          ang.add(g.pts[tie0]);
+        } else if (neq > 1) {
+          // the take lowest original indices among the ties: wth = the take-th smallest of them
+          uint32_t wth = 0xffffffffu;
+          if (neq > need) {
+            uint32_t prev = 0;
+            for (int r = 0; r < need; ++r) {
+              uint32_t best = 0xffffffffu;
+              for (int i = 0; i < vis.cnt; ++i) {
+                const float4 pt = g.pts[lp[i * 64]];
+                const uint32_t idx = __float_as_uint(pt.w);
+                if (dist2(q.x, q.y, q.z, pt) == tau && (r == 0 || idx > prev) && idx < best) best = idx;
+              }
+              prev = best;
+            }
+            wth = prev;
+            nt += static_cast<unsigned>(vis.cnt) * static_cast<unsigned>(need);
+          }
+          for (int i = 0; i < vis.cnt; ++i) {
+            const float4 pt = g.pts[lp[i * 64]];
+            if (dist2(q.x, q.y, q.z, pt) == tau && __float_as_uint(pt.w) <= wth) ang.add(pt);
+          }
+          nt += static_cast<unsigned>(vis.cnt);
+        }
+        if (nlt + take >= 3) {
+          const float mg = ang.gap();
+          gap[oi] = mg;
+          flag[oi] = mg > thr ? 1 : 0;
+        }
+      }
+    }
+  }
+  bnd_count(nt, pair_tests);
+}
+
+// The call that wants the indices: KnnVisitor's sorted (d2, original index) list for every query; nn (k
+// entries per original record, preset to -1) gets the set in that order.  A query past the ring cap is
+// listed in fb.
+__global__ __launch_bounds__(64, 1) void boundary_sorted_kernel(GridView g, size_t n, const float* __restrict__ normals,
+                                                                int k, float thr, uint8_t* __restrict__ flag,
+                                                                float* __restrict__ gap, int* __restrict__ nn,
+                                                                uint32_t* __restrict__ fb, unsigned int* __restrict__ fb_count,
+                                                                unsigned long long* __restrict__ pair_tests) {
+  const size_t t = static_cast<size_t>(blockIdx.x) * 64 + threadIdx.x;
+  const int nsent = kBndK - k;
+  unsigned nt = 0;
+  if (t < n) {
+    const float4 q = g.pts[t];
+    const uint32_t oi = __float_as_uint(q.w);
+    const float n0 = normals[3 * static_cast<size_t>(oi)], n1 = normals[3 * static_cast<size_t>(oi) + 1],
+                n2 = normals[3 * static_cast<size_t>(oi) + 2];
+    const bool has_normal = bnd_finite3(n0, n1, n2);
+    BndKnn vis;
+    vis.init(q.x, q.y, q.z, nsent);
+    ring_search(g, q.x, q.y, q.z, vis);
+    nt = vis.nt;
+    if (vis.gave_up) {
+      fb[atomicAdd(fb_count, 1u)] = static_cast<uint32_t>(t);
+    } else {
+      BndAngles ang;
+      ang.init(q, n0, n1, n2);
+      int m = 0;
+#pragma unroll
+      for (int s = 0; s < kBndK; ++s) {
+        if (s < nsent || vis.key[s] == ~0ull) continue;
+        const float4 pt = g.pts[vis.pos[s]];
+        nn[static_cast<size_t>(oi) * k + (s - nsent)] = static_cast<int>(__float_as_uint(pt.w));
+        if (has_normal) ang.add(pt);
+        ++m;
+      }
+      if (has_normal && m >= 3) {
+        const float mg = ang.gap();
+        gap[oi] = mg;
+        flag[oi] = mg > thr ? 1 : 0;
+      }
+    }
+  }
+  bnd_count(nt, pair_tests);
+}
+
+// The hand-off: one wave per listed query (sorted positions list[0 .. *count), blocks of one wave striding
+// over them).  The wave walks the rings together (wave_ring_search, the lanes' lists holding the k nearest
+// between them); a query whose neighbours lie past kBndWaveRings rings scans the whole cloud instead, lane l
+// taking points l, l + 64, ... -- exact by construction and bounded by n / 64 tests per lane, where the
+// empty rings around an outlier grow with the cube of its distance.  The k-round merge pops the keys in
+// ascending (d2, original index) order; every lane adds the same member to its own BndAngles, lane 0
+// writes.  kIdx: nn gets the set in that order.
+template <bool kIdx>
+__global__ __launch_bounds__(64, 1) void boundary_wave_kernel(GridView g, size_t n, const uint32_t* __restrict__ list,
+                                                              const unsigned int* __restrict__ count,
+                                                              const float* __restrict__ normals, int k, float thr,
+                                                              uint8_t* __restrict__ flag, float* __restrict__ gap,
+                                                              int* __restrict__ nn,
+                                                              unsigned long long* __restrict__ pair_tests) {
+  const int lane = threadIdx.x;
+  const size_t nq = static_cast<size_t>(*count);
+  unsigned long long tests = 0;  // the wave's, the same in every lane
+  for (size_t wq = blockIdx.x; wq < nq; wq += gridDim.x) {
+    const float4 q = g.pts[list[wq]];
+    const uint32_t oi = __float_as_uint(q.w);
+    const float n0 = normals[3 * static_cast<size_t>(oi)], n1 = normals[3 * static_cast<size_t>(oi) + 1],
+                n2 = normals[3 * static_cast<size_t>(oi) + 2];
+    const bool has_normal = bnd_finite3(n0, n1, n2);
+    WaveKnnLane<kBndK> L;
+    L.init();
+    if (!wave_ring_search<kBndK, true>(g, q.x, q.y, q.z, k, lane, L, kBndWaveRings, &tests)) {
+      L.init();
+      for (size_t j0 = 0; j0 < n; j0 += 256) {
+        float4 pb[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) pb[u] = g.pts[min(j0 + static_cast<size_t>(u * 64 + lane), n - 1)];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const size_t j = j0 + static_cast<size_t>(u * 64 + lane);
+          if (j >= n) continue;
+          const unsigned long long c = mkkey(dist2(q.x, q.y, q.z, pb[u]), pb[u].w);
+          if (c < L.key[kBndK - 1]) L.insert(c, static_cast<uint32_t>(j));
+        }
+      }
+      tests += n;
+    }
+    BndAngles ang;
+    ang.init(q, n0, n1, n2);
+    int m = 0;
+    for (int i = 0; i < k; ++i) {
+      const unsigned long long mk = wave_min_u64(L.key[0]);
+      if (mk == ~0ull) break;  // fewer than k points in the cloud
+      const unsigned long long win = __builtin_amdgcn_ballot_w64(L.key[0] == mk);
+      const int wl = static_cast<int>(__builtin_ctzll(win));
+      const uint32_t wp = __builtin_amdgcn_readlane(L.pos[0], wl);
+      if (lane == wl) {
+#pragma unroll
+        for (int j = 0; j < kBndK - 1; ++j) { L.key[j] = L.key[j + 1]; L.pos[j] = L.pos[j + 1]; }
+        L.key[kBndK - 1] = ~0ull;
+      }
+      const float4 pt = g.pts[wp];
+      if (kIdx && lane == 0) nn[static_cast<size_t>(oi) * k + i] = static_cast<int>(__float_as_uint(pt.w));
+      if (has_normal) ang.add(pt);
+      ++m;
+    }
+    if (has_normal && m >= 3 && lane == 0) {
+      const float mg = ang.gap();
+      gap[oi] = mg;
+      flag[oi] = mg > thr ? 1 : 0;
+    }
+  }
+  if (lane == 0 && tests) atomicAdd(pair_tests, tests);
+}
+
 __global__ __launch_bounds__(256) void reduce_finish_kernel(const double* __restrict__ partial,
                                                             int nb, double* __restrict__ out) {
   double acc[kRedVals];
@@ -4354,6 +4691,24 @@ hipError_t launch_normals_tile(const GridView& g, size_t n, float r2, const floa
   return hipGetLastError();
 }
 
+hipError_t launch_boundary(const GridView& g, size_t n, const float* normals, int k, float thr, uint8_t* flag,
+                           float* gap, int* nn, uint32_t* fb, unsigned int* fb_count,
+                           unsigned long long* pair_tests, hipStream_t s) {
+  if (!n) return hipSuccess;
+  if (k < 1 || k > kBndK) return hipErrorInvalidValue;
+  // the hand-off follows in stream order, its count read on the device; blocks past the list end at once
+  const unsigned nw = static_cast<unsigned>(std::min<size_t>(n, 4096));
+  if (nn) {
+    // the indices come in (d2, index) order from the sorted list
+    boundary_sorted_kernel<<<nblk(n, 64), 64, 0, s>>>(g, n, normals, k, thr, flag, gap, nn, fb, fb_count, pair_tests);
+    boundary_wave_kernel<true><<<nw, 64, 0, s>>>(g, n, fb, fb_count, normals, k, thr, flag, gap, nn, pair_tests);
+  } else {
+    boundary_kernel<<<nblk(n, 64), 64, 0, s>>>(g, n, normals, k, thr, flag, gap, fb, fb_count, pair_tests);
+    boundary_wave_kernel<false><<<nw, 64, 0, s>>>(g, n, fb, fb_count, normals, k, thr, flag, gap, nullptr, pair_tests);
+  }
+  return hipGetLastError();
+}
+
 hipError_t launch_reduce_finish(const double* partial, int nb, double* out, hipStream_t s) {
   reduce_finish_kernel<<<1, kRedThreads, 0, s>>>(partial, nb, out);
   return hipGetLastError();
@@ -4757,6 +5112,10 @@ hipError_t preload_kernels(void* pinned, size_t pinned_bytes, hipStream_t s) {
       reinterpret_cast<const void*>(&cc_root_kernel),
       reinterpret_cast<const void*>(&cc_emit_kernel),
       reinterpret_cast<const void*>(&normals_tile_kernel),
+      reinterpret_cast<const void*>(&boundary_kernel),
+      reinterpret_cast<const void*>(&boundary_sorted_kernel),
+      reinterpret_cast<const void*>(&boundary_wave_kernel<false>),
+      reinterpret_cast<const void*>(&boundary_wave_kernel<true>),
   };
   for (const void* f : fns) {
     hipFuncAttributes attr;

@@ -264,6 +264,29 @@ class GICPEngine:
         info = {f: getattr(ni, f) for f, _ in ni._fields_}
         return normals[:n], curvature[:n], count[:n], info
 
+    def boundary_points(self, cloud, normals, k: int = 30, angle_threshold: float = 1.047, want_gap: bool = False,
+                        want_indices: bool = False):
+        """pcl::BoundaryEstimation with a k-search (InitialAlignment::obtainBoundaryKeypoints): (boundary
+        bool[n], max_gap float32[n] | None, nn_indices int32[n, k] | None, info).  `normals` is float32
+        [n, 3] or [n, 4] (as getNormals returns it), one per record of `cloud`.  A non-finite record, a
+        record with a non-finite normal or a set without three members or without an angle is never a
+        boundary point (max_gap NaN)."""
+        _keep, ptr, n, stride = self._cloud_arg(cloud)
+        nrm = np.ascontiguousarray(normals, dtype=np.float32)
+        if nrm.ndim != 2 or nrm.shape[1] < 3 or len(nrm) != n:
+            raise ValueError(f"normals must be [{n}, 3] or [{n}, 4], got {nrm.shape}")
+        k = int(k)
+        flags = np.zeros(max(n, 1), np.uint8)
+        gap = np.zeros(max(n, 1), np.float32) if want_gap else None
+        nn = np.zeros((max(n, 1), max(k, 1)), np.int32) if want_indices else None
+        bi = _lib.MgicpBoundaryInfo()
+        self._check(self._lib.mgicp_boundary_points(
+            self._h, ctypes.c_void_p(ptr), n, stride, ctypes.c_void_p(nrm.ctypes.data), 4 * nrm.shape[1], k,
+            float(angle_threshold), flags.ctypes.data, gap.ctypes.data if want_gap else None,
+            nn.ctypes.data if want_indices else None, ctypes.byref(bi)), "boundary_points")
+        info = {f: getattr(bi, f) for f, _ in bi._fields_}
+        return (flags[:n].astype(bool), gap[:n] if want_gap else None, nn[:n] if want_indices else None, info)
+
     # -- FOD-side callers (SURVEY.md 8f rows 2 and 4) ------------------------------------------
     def segment_differences(self, cloud_in, cloud_sub, sqr_threshold: float, T=None):
         """pcl::SegmentDifferences (Filter::removeFromCloud): bool keep mask over cloud_in (after T)
