@@ -12,7 +12,7 @@ LDMAP := -Wl,--version-script=$(MAP)
 # -ffp-contract=off: no FMA contraction, so fp32/fp64 expressions round like PCL's SSE2 Eigen
 HIPFLAGS := -O3 -std=c++17 --offload-arch=$(ARCH) -fPIC -ffp-contract=off -Wall -Wno-unused-result
 
-all: $(LIB) oracle adapter-example adapter-replay fod-replay normals-replay boundary-replay
+all: $(LIB) oracle adapter-example adapter-replay fod-replay normals-replay boundary-replay fpfh-replay
 
 OBJDIR := $(PKG)/csrc/build
 OBJS  := $(OBJDIR)/mgicp_kernels.o $(OBJDIR)/mgicp_engine.o $(OBJDIR)/mgicp_clouds.o $(OBJDIR)/mgicp_pass.o \
@@ -97,6 +97,22 @@ $(BNDREPLAY): adapter/InitialAlignment_mi355x.cpp include/mi355x_gicp.h $(wildca
 
 boundary-replay: $(BNDREPLAY)
 
+# adapter/InitialAlignment_features_mi355x.cpp (InitialAlignment::obtainFeatures) compiled the same way: the
+# InitialAlignment.h of tests/adapter_standins_fpfh in front (the class with that private member, its
+# radius_factor_ and pcl::FPFHSignature33), linked with a driver that calls it on a cloud file, a normals
+# file and a keypoint index file (test infrastructure)
+STANDIN_FPFH := tests/adapter_standins_fpfh
+FPFHREPLAY   := adapter/build/replay_test_fpfh
+$(FPFHREPLAY): adapter/InitialAlignment_features_mi355x.cpp include/mi355x_gicp.h $(wildcard $(STANDIN)/*.h) \
+               $(wildcard $(STANDIN_NRM)/*.h) $(wildcard $(STANDIN_FPFH)/*.h) $(STANDIN)/Utils_standin.cpp \
+               $(STANDIN_FPFH)/replay_test_fpfh.cpp $(LIB)
+	mkdir -p adapter/build
+	g++ -O2 -std=c++14 -Wall -Wextra -Werror -I$(STANDIN_FPFH) -I$(STANDIN_NRM) -I$(STANDIN) -Iadapter -Iinclude -o $@ \
+	    adapter/InitialAlignment_features_mi355x.cpp $(STANDIN)/Utils_standin.cpp $(STANDIN_FPFH)/replay_test_fpfh.cpp \
+	    -L$(PKG) -lmgicp -Wl,-rpath,'$$ORIGIN/../../$(PKG)'
+
+fpfh-replay: $(FPFHREPLAY)
+
 oracle:
 	$(MAKE) -C oracle
 
@@ -104,4 +120,4 @@ clean:
 	rm -f $(LIB) $(PKG)/libmgicp_*.so $(OBJS)
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle clean adapter-example adapter-replay fod-replay normals-replay boundary-replay variant
+.PHONY: all oracle clean adapter-example adapter-replay fod-replay normals-replay boundary-replay fpfh-replay variant

@@ -218,6 +218,66 @@ int mgicp_boundary_points(mgicp_ctx* ctx, const float* xyz, size_t n, size_t str
                           int* nn_indices /* may be NULL, n * k */,
                           mgicp_boundary_info* info /* may be NULL */);
 
+/* InitialAlignment::obtainFeatures (src/InitialAlignment.cpp:487-508; the BOUNDARY and HARRIS methods call it
+ * at the keypoint indices, MULTISCALE's estimator is the same over every point):
+ * pcl::FPFHEstimation<PointXYZRGB, Normal, FPFHSignature33> with setRadiusSearch(radius_factor_ * resolution);
+ * PCL 1.8.1 fpfh.hpp (computeFeature, computeSPFHSignatures, computePointSPFHSignature,
+ * weightPointSPFHSignature) and pfh_tools (computePairFeatures) restated [PCL].  PCL is not available to
+ * this project's tests, so parity with PCL binaries is unpinned (README "Parity"); the rules below are
+ * the contract, and every deviation from PCL in them is deliberate.
+ * Neighbour set N(i) of a finite record i: every finite record j, i included, with FLANN's float
+ * ((dx^2) + dy^2) + dz^2 < float(radius^2), strict (the test of mgicp_radius_filter); m_i = |N(i)|.
+ * Non-finite records are in no set.
+ * SPFH row of record i: for every j in N(i), j != i, computePairFeatures(p_i, n_i, p_j, n_j) in float
+ * without FMA contraction, dots and squared norms summed as (x + y) + z: dp = p_j - p_i, f4 = |dp|; the
+ * pair is skipped when f4 == 0; a1 = n_i . dp / f4, a2 = n_j . dp / f4; if acosf(|a1|) > acosf(|a2|)
+ * the roles swap (n1 = n_j, n2 = n_i, dp = -dp, f3 = -a2), else n1 = n_i, n2 = n_j, f3 = a1;
+ * v = dp x n1, the pair is skipped when |v| == 0, else v /= |v|; w = n1 x v; f2 = v . n2;
+ * f1 = atan2f(w . n2, n1 . n2).  Bins, 11 per feature, the brackets in double as PCL's constants make
+ * them: floor(11 ((f1 + M_PI) d_pi)) with the float d_pi = 1.0f / (2.0f * (float)M_PI),
+ * floor(11 ((f2 + 1.0) 0.5)), floor(11 ((f3 + 1.0) 0.5)), each clamped to [0, 10].  A pair that is not
+ * skipped adds one count to one bin of each feature.  Deviations: (a) the row is kept as integer counts
+ * and its value is (float)count * (100.f / (float)(m_i - 1)), each rounded once -- PCL adds hist_incr
+ * repeatedly in float, in FLANN's order; as in PCL, m_i - 1 counts skipped pairs too; (b) a pair in which
+ * either normal has a non-finite component, or whose features come out NaN, is skipped -- in PCL it
+ * reaches a float-to-int cast of NaN; (c) libm's acosf / atan2f are not pinned.  m_i = 1: a zero row.
+ * Rows computed (computeSPFHSignatures): those of the union of N(q) over the keypoints q.
+ * spfh_sizes[i] = m_i for them and 0 for every other record; spfh_counts[i * 33 ..] = the bin counts
+ * (f1's 11, f2's 11, f3's 11), zero for every other record.
+ * FPFH of keypoint q (weightPointSPFHSignature): bin b = sum over the j in N(q) with float
+ * d2(q, j) != 0 of row_j[b] * w, w = 1.f / d2 (q's own row and those of exact duplicates of q are left
+ * out, as in PCL); then each feature's 11 bins are multiplied by 100.f / (their sum) when that sum is not 0.
+ * The members are added in the engine's own fixed order (ascending grid position), the feature sums in
+ * ascending bin order; FLANN's order is not reproduced.  A keypoint alone in its radius gets 33 zeros, a
+ * non-finite keypoint record 33 NaNs.  The same bits in every output on every call.
+ * keypoints: record indices in [0, n), in any order, repeats allowed; histogram k belongs to
+ * keypoints[k] (NULL: record k, and n_keypoints is ignored).  fpfh: 33 floats at the start of records of
+ * fpfh_stride_bytes (>= 132, a multiple of 4), other bytes untouched.
+ * MGICP_E_INVALID: a keypoint index outside [0, n), a negative or NaN radius, a bad pointer or stride,
+ * a set of more than 65535 records (the rows' uint16 limit; mgicp_last_error names it).  n = 0 or
+ * n_keypoints = 0: OK.  float(radius^2) = 0 links nothing: finite keypoints get zeros, every size is 0.
+ * Uses the helper cloud slot: a set source / target and their cached state stay as they are.
+ * Single rank: with a communicator attached it runs locally, without a collective. */
+typedef struct {
+    double n_finite;       /* finite records (the searched tree) */
+    double n_keypoints;    /* histograms written */
+    double n_nan;          /* of those, NaN histograms (non-finite keypoint record) */
+    double n_spfh_rows;    /* distinct records whose SPFH row was computed */
+    double pair_tests;     /* point-pair distance evaluations the device made */
+    double pair_features;  /* computePairFeatures evaluations (self and skipped pairs not counted) */
+    double ms_grid;        /* host call -> grid of the finite records built (uploads included) */
+    double ms_device;      /* first launch -> stream synchronise after the last */
+    double ms_total;       /* host call -> outputs written */
+} mgicp_fpfh_info;
+int mgicp_fpfh_features(mgicp_ctx* ctx, const float* xyz, size_t n, size_t stride_bytes,
+                        const float* normals, size_t normal_stride_bytes,
+                        const int* keypoints /* NULL: every record, in order */, size_t n_keypoints,
+                        double radius,
+                        float* fpfh, size_t fpfh_stride_bytes /* >= 132, multiple of 4; 132 = pcl::FPFHSignature33 */,
+                        uint16_t* spfh_counts /* may be NULL; n * 33 */,
+                        int* spfh_sizes /* may be NULL; n */,
+                        mgicp_fpfh_info* info /* may be NULL */);
+
 /* ---- the FOD-side callers either side of the GICP path ----
  * pcl::SegmentDifferences<PointXYZRGB>::segment as called by Filter::removeFromCloud
  * (src/Filter.cpp:176-189) on the cloud the FSM just transformed with

@@ -91,6 +91,20 @@ class MgicpBoundaryInfo(ctypes.Structure):
     ]
 
 
+class MgicpFpfhInfo(ctypes.Structure):
+    _fields_ = [
+        ("n_finite", ctypes.c_double),
+        ("n_keypoints", ctypes.c_double),
+        ("n_nan", ctypes.c_double),
+        ("n_spfh_rows", ctypes.c_double),
+        ("pair_tests", ctypes.c_double),
+        ("pair_features", ctypes.c_double),
+        ("ms_grid", ctypes.c_double),
+        ("ms_device", ctypes.c_double),
+        ("ms_total", ctypes.c_double),
+    ]
+
+
 class MgicpError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"mgicp error {code}: {msg}")
@@ -124,6 +138,8 @@ _SIGNATURES = {
                                                ctypes.POINTER(MgicpNormalsInfo)]),
     "mgicp_boundary_points": (ctypes.c_int, [_P, _P, _SZ, _SZ, _P, _SZ, ctypes.c_int, ctypes.c_double, _P, _P, _P,
                                               ctypes.POINTER(MgicpBoundaryInfo)]),
+    "mgicp_fpfh_features": (ctypes.c_int, [_P, _P, _SZ, _SZ, _P, _SZ, _P, _SZ, ctypes.c_double, _P, _SZ, _P, _P,
+                                            ctypes.POINTER(MgicpFpfhInfo)]),
     "mgicp_segment_differences": (ctypes.c_int, [_P, _FP, _P, _SZ, _SZ, _P, _SZ, _SZ, ctypes.c_double, _P,
                                                   ctypes.POINTER(_SZ)]),
     "mgicp_voxel_grid": (ctypes.c_int, [_P, _P, _SZ, _SZ, ctypes.c_int, _DP, ctypes.c_int, _P, _SZ,

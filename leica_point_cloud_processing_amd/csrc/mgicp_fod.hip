@@ -1,6 +1,6 @@
 // mgicp_fod.hip -- the product calls beside the alignment (include/mi355x_gicp.h): point transforms,
-// cloud resolution, the radius filter, radius normals, boundary points, segment differences, Euclidean
-// clustering and the voxel grid.
+// cloud resolution, the radius filter, radius normals, boundary points, FPFH descriptors, segment
+// differences, Euclidean clustering and the voxel grid.
 #pragma clang fp contract(off)
 
 #include <hip/hip_runtime.h>
@@ -268,6 +268,131 @@ int mgicp_boundary_points(mgicp_ctx* ctx, const float* xyz, size_t n, size_t str
   inf.n_boundary = static_cast<double>(n_boundary);
   inf.n_undecided = static_cast<double>(n_nan - (n - nf));  // every non-finite record has a NaN gap
   inf.pair_tests = static_cast<double>(ntests);
+  inf.ms_grid = t1 - t0;
+  inf.ms_device = t2 - t1;
+  inf.ms_total = now_ms() - t0;
+  if (info) *info = inf;
+  return MGICP_OK;
+}
+
+int mgicp_fpfh_features(mgicp_ctx* ctx, const float* xyz, size_t n, size_t stride, const float* normals,
+                        size_t normal_stride, const int* keypoints, size_t n_keypoints, double radius, float* fpfh,
+                        size_t fpfh_stride, uint16_t* spfh_counts, int* spfh_sizes, mgicp_fpfh_info* info) {
+  const size_t nk = keypoints ? n_keypoints : n;
+  if (!ctx || !(radius >= 0) || (n && (!xyz || !normals)) || (nk && !fpfh) || stride < 12 || (stride % 4) ||
+      normal_stride < 12 || (normal_stride % 4) || fpfh_stride < 132 || (fpfh_stride % 4) || n > size_t(INT32_MAX))
+    return MGICP_E_INVALID;
+  for (size_t k = 0; keypoints && k < nk; ++k)
+    if (keypoints[k] < 0 || static_cast<size_t>(keypoints[k]) >= n)
+      return fail(ctx, MGICP_E_INVALID, "keypoint index outside [0, n)");
+  HIPCK(hipSetDevice(ctx->device));
+  const double t0 = now_ms();
+  mgicp_fpfh_info inf{};
+  if (info) *info = inf;
+  if (spfh_counts && n) std::memset(spfh_counts, 0, n * 33 * sizeof(uint16_t));
+  if (spfh_sizes && n) std::memset(spfh_sizes, 0, n * sizeof(int));
+  if (n == 0 || nk == 0) return MGICP_OK;
+  // FLANN's radius: float(radius^2), strict.  0 links nothing, not even a point with itself
+  const float r2 = static_cast<float>(radius * radius);
+  double reach = radius;
+  if (r2 < 1.17549435e-38f) reach = std::max(reach, std::sqrt(static_cast<double>(r2)));
+  // the tree holds the finite records only: grid over those, at a cell edge of one radius
+  int rc = aux_grid(ctx, xyz, n, stride, r2 > 0.f ? std::min(reach, 1e30) : 0.0);
+  if (rc) return rc;
+  const size_t nf = ctx->aux.n;
+  hipStream_t s = ctx->stream;
+  unsigned char* obase = reinterpret_cast<unsigned char*>(fpfh);
+  if (nf == 0) {  // no finite record: every keypoint's is non-finite
+    for (size_t k = 0; k < nk; ++k) {
+      float* o = reinterpret_cast<float*>(obase + k * fpfh_stride);
+      for (int b = 0; b < 33; ++b) o[b] = std::nanf("");
+    }
+    inf.n_keypoints = inf.n_nan = static_cast<double>(nk);
+    inf.ms_grid = inf.ms_total = now_ms() - t0;
+    if (info) *info = inf;
+    return MGICP_OK;
+  }
+  std::vector<float> hn(3 * n);
+  const unsigned char* nbase = reinterpret_cast<const unsigned char*>(normals);
+  for (size_t i = 0; i < n; ++i) std::memcpy(&hn[3 * i], nbase + i * normal_stride, 12);
+  ScopedBuf<float> d_nrm, d_out;
+  ScopedBuf<int> d_kp, d_msize;
+  ScopedBuf<uint32_t> d_posof, d_mark, d_pos, d_list;
+  ScopedBuf<uint16_t> d_rows;
+  ScopedBuf<unsigned char> d_scratch;
+  ScopedBuf<unsigned int> d_big;
+  ScopedBuf<unsigned long long> d_ctr;
+  const size_t sb = scan_scratch_bytes(nf + 1);
+  HIPCK(d_nrm.reserve(3 * n));
+  HIPCK(d_out.reserve(nk * 33));
+  if (keypoints) HIPCK(d_kp.reserve(nk));
+  HIPCK(d_msize.reserve(nf));
+  HIPCK(d_posof.reserve(n));
+  HIPCK(d_mark.reserve(nf + 1));
+  HIPCK(d_pos.reserve(nf + 1));
+  HIPCK(d_list.reserve(nf));
+  HIPCK(d_rows.reserve(nf * 33));
+  HIPCK(d_scratch.reserve(sb));
+  HIPCK(d_big.reserve(1));
+  HIPCK(d_ctr.reserve(2 * kFpfhCtrSlots));
+  HIPCK(hipMemcpyAsync(d_nrm.p, hn.data(), 3 * n * sizeof(float), hipMemcpyHostToDevice, s));
+  if (keypoints) HIPCK(hipMemcpyAsync(d_kp.p, keypoints, nk * sizeof(int), hipMemcpyHostToDevice, s));
+  if ((rc = sync(ctx))) return rc;
+  const double t1 = now_ms();
+  // records outside the union keep a zero row and size; records outside the grid have no position
+  HIPCK(hipMemsetAsync(d_posof.p, 0xff, n * sizeof(uint32_t), s));
+  HIPCK(hipMemsetAsync(d_rows.p, 0, nf * 33 * sizeof(uint16_t), s));
+  HIPCK(hipMemsetAsync(d_msize.p, 0, nf * sizeof(int), s));
+  HIPCK(hipMemsetAsync(d_big.p, 0, sizeof(unsigned int), s));
+  HIPCK(hipMemsetAsync(d_ctr.p, 0, 2 * kFpfhCtrSlots * sizeof(unsigned long long), s));
+  const GridView& g = ctx->aux.view;
+  const int* kp = keypoints ? d_kp.p : nullptr;
+  // 1. the union of the keypoints' sets, listed; 2. its SPFH rows; 3. the keypoints' histograms
+  HIPCK(launch_fpfh_mark(g, nf, kp, nk, r2, d_posof.p, d_mark.p, d_pos.p, d_list.p, d_scratch.p, sb, d_big.p, d_ctr.p, s));
+  HIPCK(launch_fpfh_spfh(g, nf, d_list.p, d_pos.p + nf, d_nrm.p, r2, d_rows.p, d_msize.p, d_big.p, d_ctr.p, s));
+  HIPCK(launch_fpfh_final(g, kp, nk, d_posof.p, r2, d_rows.p, d_msize.p, d_big.p, d_out.p, d_ctr.p, s));
+  if ((rc = sync(ctx))) return rc;
+  const double t2 = now_ms();
+  std::vector<float> ho(nk * 33);
+  unsigned long long slots[2 * kFpfhCtrSlots], ctr[2] = {0, 0};
+  unsigned int too_big = 0;
+  uint32_t n_rows = 0;
+  HIPCK(hipMemcpyAsync(ho.data(), d_out.p, nk * 33 * sizeof(float), hipMemcpyDeviceToHost, s));
+  HIPCK(hipMemcpyAsync(slots, d_ctr.p, sizeof(slots), hipMemcpyDeviceToHost, s));
+  HIPCK(hipMemcpyAsync(&too_big, d_big.p, sizeof(too_big), hipMemcpyDeviceToHost, s));
+  HIPCK(hipMemcpyAsync(&n_rows, d_pos.p + nf, sizeof(n_rows), hipMemcpyDeviceToHost, s));
+  if ((rc = sync(ctx))) return rc;
+  for (int i = 0; i < 2 * kFpfhCtrSlots; ++i) ctr[i & 1] += slots[i];
+  if (too_big) return fail(ctx, MGICP_E_INVALID, "a neighbour set holds more than 65535 records (the limit of an SPFH row)");
+  if (spfh_counts || spfh_sizes) {  // rows and sizes come by sorted position: gather through pos_of
+    std::vector<uint32_t> pos_of(n);
+    std::vector<uint16_t> hr(spfh_counts ? nf * 33 : 0);
+    std::vector<int> hm(spfh_sizes ? nf : 0);
+    HIPCK(hipMemcpyAsync(pos_of.data(), d_posof.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (spfh_counts) HIPCK(hipMemcpyAsync(hr.data(), d_rows.p, nf * 33 * sizeof(uint16_t), hipMemcpyDeviceToHost, s));
+    if (spfh_sizes) HIPCK(hipMemcpyAsync(hm.data(), d_msize.p, nf * sizeof(int), hipMemcpyDeviceToHost, s));
+    if ((rc = sync(ctx))) return rc;
+    for (size_t i = 0; i < n; ++i) {
+      const size_t p = pos_of[i];
+      if (p >= nf) continue;  // a non-finite record: zero row, size 0
+      if (spfh_counts) std::memcpy(spfh_counts + i * 33, &hr[p * 33], 33 * sizeof(uint16_t));
+      if (spfh_sizes) spfh_sizes[i] = hm[p];
+    }
+  }
+  // a histogram is NaN exactly when its keypoint's record is not in the grid
+  const unsigned char* xbase = reinterpret_cast<const unsigned char*>(xyz);
+  size_t n_nan = 0;
+  for (size_t k = 0; k < nk; ++k) {
+    std::memcpy(obase + k * fpfh_stride, &ho[k * 33], 33 * sizeof(float));
+    const float* r = reinterpret_cast<const float*>(xbase + (keypoints ? static_cast<size_t>(keypoints[k]) : k) * stride);
+    n_nan += !(std::isfinite(r[0]) && std::isfinite(r[1]) && std::isfinite(r[2]));
+  }
+  inf.n_finite = static_cast<double>(nf);
+  inf.n_keypoints = static_cast<double>(nk);
+  inf.n_nan = static_cast<double>(n_nan);
+  inf.n_spfh_rows = static_cast<double>(n_rows);
+  inf.pair_tests = static_cast<double>(ctr[0]);
+  inf.pair_features = static_cast<double>(ctr[1]);
   inf.ms_grid = t1 - t0;
   inf.ms_device = t2 - t1;
   inf.ms_total = now_ms() - t0;

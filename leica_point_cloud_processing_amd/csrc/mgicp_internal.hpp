@@ -352,6 +352,28 @@ hipError_t launch_boundary(const GridView& g, size_t n, const float* normals, in
                            float* gap, int* nn, uint32_t* fb, unsigned int* fb_count,
                            unsigned long long* pair_tests, hipStream_t s);
 
+// FPFHEstimation with a radius search (InitialAlignment::obtainFeatures), three steps over a grid of n
+// finite points.  kp: nk original record indices in [0, records) (nullptr: 0 .. nk - 1).  Buffers by sorted
+// position: mark / pos (n + 1 words), list (n), rows (n * 33 bin counts), msize (n set sizes; rows and msize
+// zeroed by the caller); pos_of: one word per original record, preset to 0xffffffff.
+// mark: pos_of, the members of every keypoint's set "float d2 < r2" marked and listed; the number of
+// listed records lands in pos[n].  spfh: the SPFH bin counts and set size of every listed record
+// (*too_big, zeroed by the caller, = 1 when a set -- a keypoint's in mark, a row's in spfh -- exceeds
+// 65535; the steps after that leave their work undone: the call fails).  final: the weighted, normalised
+// histogram of every keypoint, 33 floats each, NaN for a record outside the grid.
+// ctr (2 * kFpfhCtrSlots words, zeroed by the caller): pairs of {distance evaluations, pair features};
+// the totals are the sums over the slots.
+constexpr int kFpfhCtrSlots = 256;
+hipError_t launch_fpfh_mark(const GridView& g, size_t n, const int* kp, size_t nk, float r2, uint32_t* pos_of,
+                            uint32_t* mark, uint32_t* pos, uint32_t* list, void* scratch, size_t scratch_bytes,
+                            unsigned int* too_big, unsigned long long* ctr, hipStream_t s);
+hipError_t launch_fpfh_spfh(const GridView& g, size_t n, const uint32_t* list, const uint32_t* count,
+                            const float* normals, float r2, uint16_t* rows, int* msize, unsigned int* too_big,
+                            unsigned long long* ctr, hipStream_t s);
+hipError_t launch_fpfh_final(const GridView& g, const int* kp, size_t nk, const uint32_t* pos_of, float r2,
+                             const uint16_t* rows, const int* msize, const unsigned int* too_big, float* out,
+                             unsigned long long* ctr, hipStream_t s);
+
 #if defined(MGICP_CORR_PHASES) && MGICP_CORR_PHASES
 hipError_t corr_phase_take(unsigned long long out[24]);  // diagnostic builds: read and reset
 #endif

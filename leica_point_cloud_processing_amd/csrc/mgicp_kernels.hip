@@ -3986,6 +3986,259 @@ __global__ __launch_bounds__(64, 1) void boundary_wave_kernel(GridView g, size_t
   if (lane == 0 && tests) atomicAdd(pair_tests, tests);
 }
 
+// ------------------------------------------------------------------------------------
+// FPFH descriptors (pcl::FPFHEstimation with a radius search, as InitialAlignment::obtainFeatures
+// calls it) -- DESIGN.md "FPFH".
+// ------------------------------------------------------------------------------------
+// One wave per item throughout (a block is one wave, so __syncthreads orders its LDS traffic): the wave
+// takes the item's cell box -- the box of normals_tile_kernel for a single query, exact for any cell
+// edge by the same argument -- through fpfh_walk, 64 candidates a turn.
+//   fpfh_mark_kernel   item = keypoint: mark[j] = 1 for every member j of its set (same-value stores);
+//                      the marked positions are then listed by an exclusive scan (fpfh_list_kernel)
+//   fpfh_spfh_kernel   item = listed record: d2 first, the pair features only for members; the 33 bin
+//                      counts are integer adds in LDS, so the order of the lanes does not matter
+//   fpfh_final_kernel  item = keypoint: lanes own bins; the members' rows are added in the walk's order
+//                      (ascending row of cells, then ascending sorted position: ballot, lowest bit
+//                      first) and the three feature sums in ascending bin order -- the same bits on
+//                      every call
+// rows / msize are indexed by sorted position, pos_of maps an original index to it (kFpfhNone: not in
+// the grid, i.e. a non-finite record).
+constexpr int kFpfhBins = 33;
+constexpr uint32_t kFpfhNone = 0xffffffffu;
+constexpr int kFpfhMaxSet = 65535;  // rows are uint16 counts
+constexpr size_t kFpfhMaxBlocks = 16384;  // one-wave blocks per launch (8 per SIMD); items beyond go round in a grid stride
+
+struct FpfhBox {
+  int xa, xb, ya, yb, za, zb;
+};
+
+__device__ __forceinline__ FpfhBox fpfh_box(const GridView& g, const float4& q, float r2) {
+  const float rx = sqrtf(r2) * 1.0001f + g.slop;
+  FpfhBox b;
+  b.xa = nrm_uniform(bcell(q.x - rx, g.ox, g.inv_h, g.nx));
+  b.xb = nrm_uniform(bcell(q.x + rx, g.ox, g.inv_h, g.nx));
+  b.ya = nrm_uniform(bcell(q.y - rx, g.oy, g.inv_h, g.ny));
+  b.yb = nrm_uniform(bcell(q.y + rx, g.oy, g.inv_h, g.ny));
+  b.za = nrm_uniform(bcell(q.z - rx, g.oz, g.inv_h, g.nz));
+  b.zb = nrm_uniform(bcell(q.z + rx, g.oz, g.inv_h, g.nz));
+  return b;
+}
+
+// f(j, ok) for every lane and every turn (ok: j is a candidate), so f may ballot and shuffle.  The box's
+// rows of cells, (z, y) ascending, are taken 64 at a time: lane l loads the range of row l, a wave prefix
+// sum lays the ranges end to end, and the candidates are dealt out 64 a turn in that order -- ascending
+// row, then ascending sorted position -- so a turn costs one round of point loads whatever the number of
+// rows it spans (a box of 3 x 3 rows with a few points each, the reference's radius, is one turn)
+template <class F>
+__device__ __forceinline__ void fpfh_walk(const GridView& g, const FpfhBox& b, int lane, F&& f) {
+  const int ys = b.yb - b.ya + 1;
+  const int nrows = (b.zb - b.za + 1) * ys;
+  for (int r0 = 0; r0 < nrows; r0 += 64) {
+    const int r = r0 + lane;
+    uint32_t a = 0, len = 0;
+    if (r < nrows) {
+      const uint32_t* row = g.cell_start + (static_cast<size_t>(b.za + r / ys) * g.ny + (b.ya + r % ys)) * g.nx;
+      a = row[b.xa];
+      len = row[b.xb + 1] - a;
+    }
+    uint32_t end = len;  // inclusive prefix sum over the lanes
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const uint32_t t = __shfl_up(end, d);
+      if (lane >= d) end += t;
+    }
+    const uint32_t total = __shfl(end, 63);
+    const int nr = min(64, nrows - r0);
+    for (uint32_t c0 = 0; c0 < total; c0 += 64) {
+      const uint32_t c = c0 + static_cast<uint32_t>(lane);
+      const bool ok = c < total;
+      int rr = 0;  // the row of candidate c: the rows whose end it has passed
+      for (int k = 0; k < nr; ++k) rr += __shfl(end, k) <= c ? 1 : 0;
+      rr = ok ? rr : 0;
+      const uint32_t ra = __shfl(a, rr), rend = __shfl(end, rr), rlen = __shfl(len, rr);
+      f(ra + (c - (rend - rlen)), ok);
+    }
+  }
+}
+
+__global__ void fpfh_index_kernel(const float4* __restrict__ pts, size_t n, uint32_t* __restrict__ pos_of) {
+  const size_t p = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (p < n) pos_of[__float_as_uint(pts[p].w)] = static_cast<uint32_t>(p);
+}
+
+__global__ __launch_bounds__(64) void fpfh_mark_kernel(GridView g, const int* __restrict__ kp, size_t nk,
+                                                       const uint32_t* __restrict__ pos_of, float r2,
+                                                       uint32_t* __restrict__ mark,
+                                                       unsigned int* __restrict__ too_big,
+                                                       unsigned long long* __restrict__ ctr) {
+  const int lane = threadIdx.x;
+  unsigned long long tests = 0;
+  for (size_t k = blockIdx.x; k < nk; k += gridDim.x) {
+    const uint32_t p = pos_of[kp ? static_cast<size_t>(kp[k]) : k];
+    if (p == kFpfhNone) continue;
+    const float4 q = g.pts[p];
+    const FpfhBox box = fpfh_box(g, q, r2);
+    int m = 0;
+    fpfh_walk(g, box, lane, [&](uint32_t j, bool ok) {
+      const bool member = ok && dist2(q.x, q.y, q.z, g.pts[j]) < r2;
+      if (member) mark[j] = 1u;
+      m += __popcll(__ballot(member));
+      tests += static_cast<unsigned long long>(__popcll(__ballot(ok)));
+    });
+    if (lane == 0 && m > kFpfhMaxSet) *too_big = 1u;  // the later steps then leave at once
+  }
+  if (lane == 0 && tests) atomicAdd(ctr + 2 * (blockIdx.x % kFpfhCtrSlots), tests);
+}
+
+__global__ void fpfh_list_kernel(const uint32_t* __restrict__ mark, const uint32_t* __restrict__ pos, size_t n,
+                                 uint32_t* __restrict__ list) {
+  const size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i < n && mark[i]) list[pos[i]] = static_cast<uint32_t>(i);
+}
+
+// PCL's computePairFeatures in float and FPFHEstimation's bin indices (the brackets in double, as PCL's
+// M_PI, 1.0 and 0.5 make them); false: the pair adds nothing (include/mi355x_gicp.h has the rules)
+__device__ __forceinline__ bool fpfh_pair_bins(const float4& pi, float nix, float niy, float niz, const float4& pj,
+                                               float njx, float njy, float njz, int& b1, int& b2, int& b3) {
+  if (!(isfinite(nix) && isfinite(niy) && isfinite(niz) && isfinite(njx) && isfinite(njy) && isfinite(njz)))
+    return false;
+  float dx = pj.x - pi.x, dy = pj.y - pi.y, dz = pj.z - pi.z;
+  const float f4 = sqrtf((dx * dx + dy * dy) + dz * dz);
+  if (f4 == 0.f) return false;
+  const float a1 = ((nix * dx + niy * dy) + niz * dz) / f4;
+  const float a2 = ((njx * dx + njy * dy) + njz * dz) / f4;
+  float n1x = nix, n1y = niy, n1z = niz, n2x = njx, n2y = njy, n2z = njz, f3 = a1;
+  if (acosf(fabsf(a1)) > acosf(fabsf(a2))) {
+    n1x = njx, n1y = njy, n1z = njz;
+    n2x = nix, n2y = niy, n2z = niz;
+    dx = -dx, dy = -dy, dz = -dz;
+    f3 = -a2;
+  }
+  float vx = dy * n1z - dz * n1y, vy = dz * n1x - dx * n1z, vz = dx * n1y - dy * n1x;
+  const float vn = sqrtf((vx * vx + vy * vy) + vz * vz);
+  if (vn == 0.f) return false;
+  vx /= vn, vy /= vn, vz /= vn;
+  const float wx = n1y * vz - n1z * vy, wy = n1z * vx - n1x * vz, wz = n1x * vy - n1y * vx;
+  const float f2 = (vx * n2x + vy * n2y) + vz * n2z;
+  const float f1 = atan2f((wx * n2x + wy * n2y) + wz * n2z, (n1x * n2x + n1y * n2y) + n1z * n2z);
+  if (!(f1 == f1 && f2 == f2 && f3 == f3)) return false;
+  const float d_pi = 1.0f / (2.0f * 3.14159265358979323846f);
+  const double t1 = floor(11.0 * ((static_cast<double>(f1) + 3.14159265358979323846) * static_cast<double>(d_pi)));
+  const double t2 = floor(11.0 * ((static_cast<double>(f2) + 1.0) * 0.5));
+  const double t3 = floor(11.0 * ((static_cast<double>(f3) + 1.0) * 0.5));
+  b1 = static_cast<int>(fmin(fmax(t1, 0.0), 10.0));
+  b2 = static_cast<int>(fmin(fmax(t2, 0.0), 10.0));
+  b3 = static_cast<int>(fmin(fmax(t3, 0.0), 10.0));
+  return true;
+}
+
+// ctr: kFpfhCtrSlots pairs of {pair tests, pair features}, a block adding to the pair of its index modulo
+// the slots -- one address for every wave's add costs more than the kernels' work (65536 waves took
+// 0.8 ms to add one word each); the host sums the slots.  *too_big = 1 when a set exceeds kFpfhMaxSet -- the call then
+// fails, so a wave that finds the flag set (by the mark step or by another row) stops
+__global__ __launch_bounds__(64) void fpfh_spfh_kernel(GridView g, const uint32_t* __restrict__ list,
+                                                       const uint32_t* __restrict__ count,
+                                                       const float* __restrict__ normals, float r2,
+                                                       uint16_t* __restrict__ rows, int* __restrict__ msize,
+                                                       unsigned int* __restrict__ too_big,
+                                                       unsigned long long* __restrict__ ctr) {
+  __shared__ int hist[kFpfhBins];
+  const int lane = threadIdx.x;
+  const uint32_t nl = *count;
+  unsigned long long tests = 0, feats = 0;
+  for (uint32_t idx = blockIdx.x; idx < nl; idx += gridDim.x) {
+    if (__hip_atomic_load(too_big, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
+    const uint32_t p = list[idx];
+    const float4 q = g.pts[p];
+    const size_t oi = __float_as_uint(q.w);
+    const float nix = normals[3 * oi], niy = normals[3 * oi + 1], niz = normals[3 * oi + 2];
+    if (lane < kFpfhBins) hist[lane] = 0;
+    __syncthreads();
+    const FpfhBox box = fpfh_box(g, q, r2);
+    int m = 0;
+    fpfh_walk(g, box, lane, [&](uint32_t j, bool ok) {
+      bool member = false, feat = false;
+      if (ok) {
+        const float4 pj = g.pts[j];
+        member = dist2(q.x, q.y, q.z, pj) < r2;
+        if (member && j != p) {
+          const size_t oj = __float_as_uint(pj.w);
+          int b1, b2, b3;
+          feat = fpfh_pair_bins(q, nix, niy, niz, pj, normals[3 * oj], normals[3 * oj + 1], normals[3 * oj + 2], b1,
+                                b2, b3);
+          if (feat) {
+            atomicAdd(&hist[b1], 1);
+            atomicAdd(&hist[11 + b2], 1);
+            atomicAdd(&hist[22 + b3], 1);
+          }
+        }
+      }
+      tests += static_cast<unsigned long long>(__popcll(__ballot(ok)));
+      feats += static_cast<unsigned long long>(__popcll(__ballot(feat)));
+      m += __popcll(__ballot(member));
+    });
+    __syncthreads();
+    if (lane < kFpfhBins) rows[static_cast<size_t>(p) * kFpfhBins + lane] = static_cast<uint16_t>(min(hist[lane], kFpfhMaxSet));
+    if (lane == 0) {
+      msize[p] = m;
+      if (m > kFpfhMaxSet) *too_big = 1u;
+    }
+    __syncthreads();
+  }
+  if (lane == 0 && tests) atomicAdd(ctr + 2 * (blockIdx.x % kFpfhCtrSlots), tests);
+  if (lane == 0 && feats) atomicAdd(ctr + 2 * (blockIdx.x % kFpfhCtrSlots) + 1, feats);
+}
+
+__global__ __launch_bounds__(64) void fpfh_final_kernel(GridView g, const int* __restrict__ kp, size_t nk,
+                                                        const uint32_t* __restrict__ pos_of, float r2,
+                                                        const uint16_t* __restrict__ rows,
+                                                        const int* __restrict__ msize,
+                                                        const unsigned int* __restrict__ too_big,
+                                                        float* __restrict__ out,
+                                                        unsigned long long* __restrict__ ctr) {
+  const int lane = threadIdx.x;
+  const int bin = lane < kFpfhBins ? lane : 0;
+  unsigned long long tests = 0;
+  if (*too_big) return;
+  for (size_t k = blockIdx.x; k < nk; k += gridDim.x) {
+    const uint32_t p = pos_of[kp ? static_cast<size_t>(kp[k]) : k];
+    float* o = out + k * kFpfhBins;
+    if (p == kFpfhNone) {
+      if (lane < kFpfhBins) o[lane] = __uint_as_float(0x7fc00000u);
+      continue;
+    }
+    const float4 q = g.pts[p];
+    const FpfhBox box = fpfh_box(g, q, r2);
+    float acc = 0.f;
+    fpfh_walk(g, box, lane, [&](uint32_t j, bool ok) {
+      const float d2 = ok ? dist2(q.x, q.y, q.z, g.pts[j]) : INFINITY;
+      unsigned long long hits = __ballot(ok && d2 < r2 && d2 != 0.f);
+      tests += static_cast<unsigned long long>(__popcll(__ballot(ok)));
+      while (hits) {
+        const int b = __ffsll(static_cast<long long>(hits)) - 1;
+        hits &= hits - 1;
+        const uint32_t jj = __shfl(j, b);
+        const float dd = __shfl(d2, b);
+        const int mj = msize[jj];
+        if (mj > 1) {
+          const float s = 100.f / static_cast<float>(mj - 1);
+          const float w = 1.f / dd;
+          const float val = static_cast<float>(rows[static_cast<size_t>(jj) * kFpfhBins + bin]) * s;
+          acc = acc + val * w;
+        }
+      }
+    });
+    // each feature's 11 bins, summed in ascending bin order by every lane of the feature
+    const int f0 = (bin / 11) * 11;
+    float sum = 0.f;
+#pragma unroll
+    for (int t = 0; t < 11; ++t) sum = sum + __shfl(acc, f0 + t);
+    if (sum != 0.f) acc = acc * (100.f / sum);
+    if (lane < kFpfhBins) o[lane] = acc;
+  }
+  if (lane == 0 && tests) atomicAdd(ctr + 2 * (blockIdx.x % kFpfhCtrSlots), tests);
+}
+
 __global__ __launch_bounds__(256) void reduce_finish_kernel(const double* __restrict__ partial,
                                                             int nb, double* __restrict__ out) {
   double acc[kRedVals];
@@ -4709,6 +4962,45 @@ hipError_t launch_boundary(const GridView& g, size_t n, const float* normals, in
   return hipGetLastError();
 }
 
+hipError_t launch_fpfh_mark(const GridView& g, size_t n, const int* kp, size_t nk, float r2, uint32_t* pos_of,
+                            uint32_t* mark, uint32_t* pos, uint32_t* list, void* scratch, size_t scratch_bytes,
+                            unsigned int* too_big, unsigned long long* ctr, hipStream_t s) {
+  if (!n) return hipSuccess;
+  fpfh_index_kernel<<<nblk(n), 256, 0, s>>>(g.pts, n, pos_of);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  if (kp || !(r2 > 0.f)) {
+    if ((e = hipMemsetAsync(mark, 0, (n + 1) * sizeof(uint32_t), s)) != hipSuccess) return e;
+    if (nk) fpfh_mark_kernel<<<static_cast<unsigned>(std::min<size_t>(nk, kFpfhMaxBlocks)), 64, 0, s>>>(g, kp, nk, pos_of, r2, mark, too_big, ctr);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  } else {
+    // every record is a keypoint and in its own set (d2 = 0 < r2): every row is wanted
+    if ((e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(mark), 1, n, s)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(mark + n, 0, sizeof(uint32_t), s)) != hipSuccess) return e;
+  }
+  if ((e = launch_exclusive_scan(scratch, scratch_bytes, mark, pos, n + 1, s)) != hipSuccess) return e;
+  fpfh_list_kernel<<<nblk(n), 256, 0, s>>>(mark, pos, n, list);
+  return hipGetLastError();
+}
+
+hipError_t launch_fpfh_spfh(const GridView& g, size_t n, const uint32_t* list, const uint32_t* count,
+                            const float* normals, float r2, uint16_t* rows, int* msize, unsigned int* too_big,
+                            unsigned long long* ctr, hipStream_t s) {
+  if (!n) return hipSuccess;
+  // the list's length is read on the device; blocks past its end leave at once
+  fpfh_spfh_kernel<<<static_cast<unsigned>(std::min<size_t>(n, kFpfhMaxBlocks)), 64, 0, s>>>(g, list, count, normals, r2, rows, msize,
+                                                                          too_big, ctr);
+  return hipGetLastError();
+}
+
+hipError_t launch_fpfh_final(const GridView& g, const int* kp, size_t nk, const uint32_t* pos_of, float r2,
+                             const uint16_t* rows, const int* msize, const unsigned int* too_big, float* out,
+                             unsigned long long* ctr, hipStream_t s) {
+  if (!nk) return hipSuccess;
+  fpfh_final_kernel<<<static_cast<unsigned>(std::min<size_t>(nk, kFpfhMaxBlocks)), 64, 0, s>>>(g, kp, nk, pos_of, r2, rows, msize, too_big, out, ctr);
+  return hipGetLastError();
+}
+
 hipError_t launch_reduce_finish(const double* partial, int nb, double* out, hipStream_t s) {
   reduce_finish_kernel<<<1, kRedThreads, 0, s>>>(partial, nb, out);
   return hipGetLastError();
@@ -5116,6 +5408,11 @@ hipError_t preload_kernels(void* pinned, size_t pinned_bytes, hipStream_t s) {
       reinterpret_cast<const void*>(&boundary_sorted_kernel),
       reinterpret_cast<const void*>(&boundary_wave_kernel<false>),
       reinterpret_cast<const void*>(&boundary_wave_kernel<true>),
+      reinterpret_cast<const void*>(&fpfh_index_kernel),
+      reinterpret_cast<const void*>(&fpfh_mark_kernel),
+      reinterpret_cast<const void*>(&fpfh_list_kernel),
+      reinterpret_cast<const void*>(&fpfh_spfh_kernel),
+      reinterpret_cast<const void*>(&fpfh_final_kernel),
   };
   for (const void* f : fns) {
     hipFuncAttributes attr;

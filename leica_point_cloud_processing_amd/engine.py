@@ -287,6 +287,31 @@ class GICPEngine:
         info = {f: getattr(bi, f) for f, _ in bi._fields_}
         return (flags[:n].astype(bool), gap[:n] if want_gap else None, nn[:n] if want_indices else None, info)
 
+    def fpfh_features(self, cloud, normals, keypoints=None, radius: float = 0.0, want_spfh: bool = False):
+        """pcl::FPFHEstimation with a radius search (InitialAlignment::obtainFeatures): (fpfh float32
+        [nk, 33], spfh_counts uint16[n, 33] | None, spfh_sizes int32[n] | None, info).  `normals` is float32
+        [n, 3] or [n, 4], one per record of `cloud`; `keypoints` are record indices in any order, repeats
+        allowed (None: every record).  Row k is the histogram of keypoints[k]: NaN for a non-finite record,
+        zeros for a record alone in its radius.  With want_spfh, the SPFH bin counts and set sizes of the
+        records within the radius of some keypoint (zero elsewhere)."""
+        _keep, ptr, n, stride = self._cloud_arg(cloud)
+        nrm = np.ascontiguousarray(normals, dtype=np.float32)
+        if nrm.ndim != 2 or nrm.shape[1] < 3 or len(nrm) != n:
+            raise ValueError(f"normals must be [{n}, 3] or [{n}, 4], got {nrm.shape}")
+        kp = None if keypoints is None else np.ascontiguousarray(keypoints, dtype=np.int32).reshape(-1)
+        nk = n if kp is None else len(kp)
+        fpfh = np.zeros((max(nk, 1), 33), np.float32)
+        counts = np.zeros((max(n, 1), 33), np.uint16) if want_spfh else None
+        sizes = np.zeros(max(n, 1), np.int32) if want_spfh else None
+        fi = _lib.MgicpFpfhInfo()
+        self._check(self._lib.mgicp_fpfh_features(
+            self._h, ctypes.c_void_p(ptr), n, stride, ctypes.c_void_p(nrm.ctypes.data), 4 * nrm.shape[1],
+            ctypes.c_void_p(kp.ctypes.data) if kp is not None else None, nk, float(radius), fpfh.ctypes.data, 132,
+            counts.ctypes.data if want_spfh else None, sizes.ctypes.data if want_spfh else None, ctypes.byref(fi)),
+            "fpfh_features")
+        info = {f: getattr(fi, f) for f, _ in fi._fields_}
+        return (fpfh[:nk], counts[:n] if want_spfh else None, sizes[:n] if want_spfh else None, info)
+
     # -- FOD-side callers (SURVEY.md 8f rows 2 and 4) ------------------------------------------
     def segment_differences(self, cloud_in, cloud_sub, sqr_threshold: float, T=None):
         """pcl::SegmentDifferences (Filter::removeFromCloud): bool keep mask over cloud_in (after T)

@@ -1,9 +1,9 @@
 """InitialAlignment -- the pre-alignment's steps that run on the MI355X engine.
 
-So far one member of the reference class (src/InitialAlignment.cpp): obtainBoundaryKeypoints, the keypoint
-step of the BOUNDARY (default) and NORMALS methods.  The normals it takes come from
-gicp_alignment.getNormals (Utils::getNormals); FPFH at the keypoints, the feature correspondences and the
-RANSAC rejector are not on the engine yet.
+Two members of the reference class (src/InitialAlignment.cpp): obtainBoundaryKeypoints, the keypoint step
+of the BOUNDARY (default) and NORMALS methods, and obtainFeatures, the FPFH descriptors at the keypoints
+(BOUNDARY and HARRIS).  The normals they take come from gicp_alignment.getNormals (Utils::getNormals); the
+feature correspondences and the RANSAC rejector are not on the engine yet.
 """
 from __future__ import annotations
 
@@ -14,6 +14,7 @@ from .engine import GICPEngine
 
 BOUNDARY_K_SEARCH = 30             # detector.setKSearch(30)
 BOUNDARY_ANGLE_THRESHOLD = 1.047   # detector.setAngleThreshold(1.047f)
+RADIUS_FACTOR = 1.4                # radius_factor_ (the constructor's default)
 
 
 def obtainBoundaryKeypoints(cloud, normals, engine: GICPEngine | None = None):
@@ -36,3 +37,26 @@ def obtainBoundaryKeypoints(cloud, normals, engine: GICPEngine | None = None):
     keypoints = np.flatnonzero(boundary).astype(np.int32)
     non_keypoints = np.flatnonzero(~boundary).astype(np.int32)
     return (-1 if len(keypoints) == 0 else 0), keypoints, non_keypoints
+
+
+def obtainFeatures(cloud, normals, keypoints_indices, radius_factor: float = RADIUS_FACTOR,
+                   engine: GICPEngine | None = None):
+    """InitialAlignment::obtainFeatures (src/InitialAlignment.cpp:487-508): pcl::FPFHEstimation at
+    `keypoints_indices` with a radius search of radius_factor * computeCloudResolution(cloud).  `normals` is
+    float32 [n, 3] or [n, 4] (getNormals' array).  Returns (status, features): features float32
+    [len(keypoints_indices), 33], one FPFHSignature33 per keypoint in the order given; status -1 when no
+    feature comes back (no keypoint, or normals that do not match the cloud: PCL's initCompute fails and
+    the output stays empty), else 0."""
+    size = cloud.size() if isinstance(cloud, PointCloudRGB) else len(np.asarray(cloud).reshape(-1, 3))
+    normals = np.asarray(normals, dtype=np.float32)
+    keypoints = np.asarray(keypoints_indices, dtype=np.int32).reshape(-1)
+    empty = np.zeros((0, 33), np.float32)
+    if normals.ndim != 2 or len(normals) != size or len(keypoints) == 0:
+        return -1, empty
+    if engine is None:
+        from .filter import _engine
+
+        engine = _engine()
+    radius = engine.cloud_resolution(cloud) * radius_factor
+    features, _counts, _sizes, _info = engine.fpfh_features(cloud, normals, keypoints, radius)
+    return (-1 if len(features) == 0 else 0), features
