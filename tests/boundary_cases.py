@@ -207,7 +207,8 @@ def comparable(ref, thr=THRESHOLD):
 # the cases: name -> (xyz float32 [n, 3], normals float32 [n, 3], k)
 # ---------------------------------------------------------------------------------------
 CASES = ("cube", "part", "part_small", "nonfinite", "huge_radius", "clump", "lattice", "outliers", "k7", "k32",
-         "few", "dups", "one_angle", "pile")
+         "few", "dups", "one_angle", "pile") + nc.FAR_CASES
+TIE_CASES = ("lattice", "pile", "lattice_rim")  # the cases built for float d2 ties across the k-th place
 
 
 def truth_normals(xyz, radius):
@@ -299,8 +300,15 @@ def pile():
 @functools.lru_cache(maxsize=None)
 def case(name):
     """(xyz, normals, k)"""
-    if name in ("cube", "part", "part_small", "nonfinite", "huge_radius"):
+    if name in ("cube", "part", "part_small", "nonfinite", "huge_radius") + tuple(nc.FAR_PART_OFFSET):
         return _from_normals_case(name) + (K_DEFAULT,)
+    # the far frames of normals_cases: a dense sheet whose grid slop is several cell edges (the stop test's
+    # bound stays non-positive for the first rings, so ordinary queries may reach the ring cap and take the
+    # hand-off), and the lattice whose d2 tie across the k-th place in a frame of 2^-11 steps
+    if name in nc.FAR_SHEET_X0:
+        return nc.far_sheet(name)[0], nc.far_sheet_normals(name), K_DEFAULT
+    if name == "lattice_rim":
+        return nc.lattice_rim()[0], nc.lattice_rim_normals(), K_DEFAULT
     if name == "clump":
         return _from_normals_case("clump") + (32,)
     if name == "k7":

@@ -247,9 +247,13 @@ def histograms(ref, keypoints, counts):
 # ---------------------------------------------------------------------------------------
 # the cases: name -> (xyz float32 [n, 3], normals float32 [n, 3], keypoints int32 | None, radius)
 # ---------------------------------------------------------------------------------------
-CASES = ("part_kp", "part_3res", "part_all", "cube", "clump", "huge_radius", "nonfinite", "dups", "shuffled",
-         "radius_zero", "n0", "n1", "n2", "n3")
-CLOUD_CASES = CASES[:9]     # the cases with neighbourhoods (the others are edge values)
+FAR_PART_CASES = {"far_part300_kp": ("far_part300", 1.4), "far_part300_3res": ("far_part300", 3.0),
+                  "far_part4096_kp": ("far_part4096", 1.4), "far_part4096_3res": ("far_part4096", 3.0)}
+FAR_CASES = tuple(nc.FAR_SHEET_X0) + tuple(FAR_PART_CASES) + ("lattice_rim",)
+EDGE_VALUE_CASES = ("radius_zero", "n0", "n1", "n2", "n3")
+CASES = ("part_kp", "part_3res", "part_all", "cube", "clump", "huge_radius", "nonfinite", "dups",
+         "shuffled") + FAR_CASES + EDGE_VALUE_CASES
+CLOUD_CASES = CASES[:-len(EDGE_VALUE_CASES)]     # the cases with neighbourhoods (the others are edge values)
 
 
 @functools.lru_cache(maxsize=None)
@@ -264,14 +268,7 @@ def _part():
     return scan, nrm, kp, res
 
 
-def _tilted(nrm, seed, sigma=0.02):
-    """unit normals tilted by a few hundredths of a radian each: on a flat patch estimated normals agree to
-    the last bit, and two equal normals make a1 = a2 exactly -- a tie of the role assignment between
-    branches with different f3 bins, which the firm flag rightly leaves out but a case must not consist of"""
-    rng = np.random.default_rng(seed)
-    t = nrm.astype(np.float64) + sigma * rng.normal(size=nrm.shape)
-    with np.errstate(invalid="ignore"):
-        return (t / np.linalg.norm(t, axis=1)[:, None]).astype(np.float32)
+_tilted = nc.tilted
 
 
 @functools.lru_cache(maxsize=None)
@@ -345,8 +342,42 @@ def shuffled():
 
 
 @functools.lru_cache(maxsize=None)
+def _far_part(which):
+    """_part()'s recipe in a site frame: the 3000 shifted records, their truth normals (radius 10
+    resolutions), the truth boundary keypoints of that frame, the resolution"""
+    xyz, nrm, _k = bc.case(which)
+    ref = bc.case_reference(which)
+    with np.errstate(invalid="ignore"):
+        kp = np.flatnonzero(ref.decided & (ref.truth > np.float64(np.float32(bc.THRESHOLD)))).astype(np.int32)
+    return xyz, nrm, kp, nc._far_part_base()[1]
+
+
+def far_sheet(name):
+    """normals_cases.far_sheet with its tilted plane normals at the normals' radius of 1.2 mm, every fifth
+    record a keypoint: at |X0| = 4096.5 a record's cell box has 80-100 rows of cells -- fpfh_walk's outer
+    loop takes a second turn of 64 rows -- where the control at X0 = 0 has at most 16"""
+    xyz, radius = nc.far_sheet(name)
+    return xyz, nc.far_sheet_normals(name), np.arange(0, len(xyz), 5, dtype=np.int32), radius
+
+
+def lattice_rim():
+    """normals_cases.lattice_rim with its tilted normals, every fifth record a keypoint: set sizes decided by
+    pairs at d2 == r2 and one float step below"""
+    xyz, radius = nc.lattice_rim()
+    return xyz, nc.lattice_rim_normals(), np.arange(0, len(xyz), 5, dtype=np.int32), radius
+
+
+@functools.lru_cache(maxsize=None)
 def case(name):
     """(xyz, normals, keypoints | None, radius)"""
+    if name in FAR_PART_CASES:
+        which, factor = FAR_PART_CASES[name]
+        xyz, nrm, kp, res = _far_part(which)
+        return xyz, nrm, kp, factor * res
+    if name in nc.FAR_SHEET_X0:
+        return far_sheet(name)
+    if name == "lattice_rim":
+        return lattice_rim()
     if name in ("part_kp", "part_3res", "part_all"):
         scan, nrm, kp, res = _part()
         return scan, nrm, (None if name == "part_all" else kp), (1.4 if name == "part_kp" else 3.0) * res

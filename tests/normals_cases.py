@@ -14,14 +14,15 @@ the neighbour sets (exact counts), and per record
             eigenvector is then taken in fp64 (so its error is that of the sums alone: a lower bound).
 `grid_of` (tests/cluster_edges_cases.py) restates the engine's cell index ONLY to certify that a cloud
 reaches a regime of the kernel (a cell with more points than a block has lanes, a neighbourhood larger
-than one staging chunk, a cell edge grown past the radius); it never produces an expected result.
+than one staging chunk, a cell edge grown past the radius, a cell box widened by the slop of a far frame:
+`box_facts`); it never produces an expected result.
 """
 import functools
 import os
 
 import numpy as np
 
-from cluster_edges_cases import cell_counts, d2_f32, r2_of
+from cluster_edges_cases import cell_counts, d2_f32, grid_of, r2_of
 
 BLOCK_LANES = 64     # kNrmThreads: queries one block holds
 STAGE_POINTS = 512   # kNrmStage: points per staged chunk
@@ -188,8 +189,26 @@ def view_dot(xyz, normals, viewpoint=(0.0, 0.0, 0.0)):
 # ---------------------------------------------------------------------------------------
 # the cases: name -> (xyz float32 [n, 3], radius)
 # ---------------------------------------------------------------------------------------
-DIRECTION_CASES = ("cube", "part", "part_small", "clump", "huge_radius", "tiny_radius", "nonfinite")
+FAR_SHEET_X0 = {"far_sheet": 4096.5, "far_sheet_neg": -4096.5, "far_sheet_origin": 0.0}
+FAR_PART_OFFSET = {"far_part300": "site300", "far_part4096": "site4096"}  # keys of geometry_edges_cases.OFFSETS
+FAR_CASES = tuple(FAR_SHEET_X0) + tuple(FAR_PART_OFFSET) + ("lattice_rim",)
+DIRECTION_CASES = ("cube", "part", "part_small", "clump", "huge_radius", "tiny_radius", "nonfinite") + FAR_CASES
 VIEWPOINT = (1.0, -2.0, 5.0)  # the non-default viewpoint of the `part` case
+
+
+def _site_offset(name):
+    from geometry_edges_cases import OFFSETS
+
+    return OFFSETS[FAR_PART_OFFSET[name]]
+
+
+def viewpoints():
+    """name -> the non-default viewpoint of the case: VIEWPOINT, moved with the cloud in the far frames (the
+    default one, the origin, is then kilometres away from the part)"""
+    vp = {"part": VIEWPOINT, "far_sheet_origin": VIEWPOINT}  # the control's sheet passes through the origin
+    for name in FAR_PART_OFFSET:
+        vp[name] = tuple(float(v) for v in np.asarray(VIEWPOINT, np.float32) + np.asarray(_site_offset(name), np.float32))
+    return vp
 
 
 @functools.lru_cache(maxsize=None)
@@ -285,6 +304,93 @@ def nonfinite():
     return bad, 14.0 * res
 
 
+def tilted(nrm, seed, sigma=0.02):
+    """unit normals tilted by a few hundredths of a radian each: on a flat patch estimated normals agree to
+    the last bit, and two equal normals make a1 = a2 exactly -- a tie of the role assignment between
+    branches with different f3 bins, which the firm flag rightly leaves out but a case must not consist of"""
+    rng = np.random.default_rng(seed)
+    t = nrm.astype(np.float64) + sigma * rng.normal(size=nrm.shape)
+    with np.errstate(invalid="ignore"):
+        return (t / np.linalg.norm(t, axis=1)[:, None]).astype(np.float32)
+
+
+# ---- far frames (DESIGN.md "Site frames"): slop larger than the radius, site offsets, pairs at the rim
+FAR_SHEET_RADIUS = 1.2e-3
+FAR_SHEET_PLANE = (1.0, -0.3, 0.2)      # the sheet's normal, not normalised
+LATTICE_RIM_STEP = 2.0 ** -11           # the float step of every coordinate of lattice_rim
+LATTICE_RIM_OFF = (4096.5, -4100.25, 5000.75)
+LATTICE_RIM_RADIUS = 5 * LATTICE_RIM_STEP
+
+
+@functools.lru_cache(maxsize=None)
+def far_sheet(name="far_sheet"):
+    """6000 points of a noisy tilted sheet 3 cm x 3 cm, x = X0 + 0.3 y - 0.2 z + N(0, 5e-5), at a radius of
+    1.2 mm.  At |X0| = 4096.5 the grid's slop (8 float steps of the largest coordinate, 3.9 mm) is three
+    radii: a cell box is 9-10 cells wide where the same cloud at X0 = 0 (the control: the same draws) has
+    boxes of at most 4 x 4 rows; x itself is cut to steps of 0.49 mm there.  -4096.5 is the mirrored side of
+    every clamp and floor."""
+    x0 = FAR_SHEET_X0[name]
+    rng = np.random.default_rng(31)
+    y = rng.uniform(0.0, 0.03, 6000)
+    z = rng.uniform(0.0, 0.03, 6000)
+    x = x0 + 0.3 * y - 0.2 * z + rng.normal(0.0, 5e-5, 6000)
+    return np.ascontiguousarray(np.stack([x, y, z], 1), np.float32), FAR_SHEET_RADIUS
+
+
+@functools.lru_cache(maxsize=None)
+def far_sheet_normals(name="far_sheet"):
+    """the sheet's plane normal, tilted by 0.02 rad per record: what the boundary and FPFH cases are given"""
+    n = np.asarray(FAR_SHEET_PLANE) / np.linalg.norm(FAR_SHEET_PLANE)
+    return tilted(np.tile(n, (6000, 1)), 33, sigma=0.02)
+
+
+@functools.lru_cache(maxsize=None)
+def _far_part_base():
+    """the first 3000 records of the part's scan and their resolution (in the scan's own frame)"""
+    scan, _res = _part_scan()
+    base = np.ascontiguousarray(scan[:3000])
+    return base, resolution(base)
+
+
+@functools.lru_cache(maxsize=None)
+def far_part(name):
+    """3000 records of the part's scan moved by a site offset in float32, radius 10 resolutions: a
+    metres-wide part whose coordinates have 2^-15 (site300) or 2^-11 m (site4096) steps"""
+    from geometry_edges_cases import shifted
+
+    base, res = _far_part_base()
+    return shifted(base, _site_offset(name)), 10.0 * res
+
+
+@functools.lru_cache(maxsize=None)
+def lattice_rim_ij():
+    """integer lattice coordinates of lattice_rim: 6000 draws in [0, 60) x [0, 60) x [0, 6), made unique,
+    permuted"""
+    rng = np.random.default_rng(41)
+    ij = np.unique(rng.integers(0, [60, 60, 6], (6000, 3)), axis=0)
+    return np.ascontiguousarray(ij[rng.permutation(len(ij))], np.int64)
+
+
+@functools.lru_cache(maxsize=None)
+def lattice_rim():
+    """off + ij 2^-11 with every coordinate in [4096, 8192) in magnitude: each is a multiple of its float
+    step, so every float d2 is an exact integer times 2^-22, and with radius = 5 steps float(radius^2) is
+    exactly 25 of them.  Thousands of pairs sit at d2 == r2 (rejected: the test is strict) and one step below
+    (24 = 16 + 4 + 4, accepted): the neighbour sets are decided by strictness alone, in a frame whose slop is
+    two radii."""
+    xyz64 = np.asarray(LATTICE_RIM_OFF) + lattice_rim_ij() * LATTICE_RIM_STEP
+    xyz = xyz64.astype(np.float32)
+    assert (xyz.astype(np.float64) == xyz64).all()
+    return np.ascontiguousarray(xyz), LATTICE_RIM_RADIUS
+
+
+@functools.lru_cache(maxsize=None)
+def lattice_rim_normals():
+    """(0.1, -0.2, 1) normalised, tilted by 0.05 rad per record"""
+    n = np.array([0.1, -0.2, 1.0]) / np.sqrt(1.05)
+    return tilted(np.tile(n, (len(lattice_rim_ij()), 1)), 43, sigma=0.05)
+
+
 @functools.lru_cache(maxsize=None)
 def degenerate():
     """Duplicated points and a collinear run, each out of reach of everything else, beside a small sheet.
@@ -316,6 +422,12 @@ def edge_clouds():
 
 def case(name):
     """(xyz, radius) of a direction case"""
+    if name in FAR_SHEET_X0:
+        return far_sheet(name)
+    if name in FAR_PART_OFFSET:
+        return far_part(name)
+    if name == "lattice_rim":
+        return lattice_rim()
     return {"cube": cube, "part": part, "part_small": part_small, "clump": clump, "huge_radius": huge_radius,
             "tiny_radius": tiny_radius, "nonfinite": nonfinite}[name]()
 
@@ -332,3 +444,31 @@ def grid_facts(xyz, radius):
     its tolerance)."""
     g, _keys, counts = cell_counts(xyz, 2.0 * radius)
     return float(g.h), int(counts.max()), list(g.dims)
+
+
+def box_facts(xyz, radius):
+    """(rows, points, rx / h) of the cell box of every record taken as a single query (fpfh_box; a group of
+    normals_tile_kernel has a box at least as large): rows of cells (y, z) and the points inside.  A float32
+    restatement of rx = sqrtf(r2) * 1.0001f + slop, slop = 8 maxabs 2^-23 + 1e-6 h, over grid_of's cells.
+    Like grid_of it only certifies that a cloud reaches a regime; it never produces an expected result."""
+    f32 = np.float32
+    xyz = np.asarray(xyz, f32).reshape(-1, 3)
+    assert np.isfinite(xyz).all()
+    g = grid_of(xyz, 2.0 * radius)
+    slop = f32(f32(f32(8.0) * np.abs(xyz).max()) * f32(1.1920929e-7)) + f32(f32(1e-6) * f32(g.h))
+    rx = f32(f32(np.sqrt(r2_of(radius))) * f32(1.0001)) + f32(slop)
+    lo, hi = g.cells((xyz - rx).astype(f32)), g.cells((xyz + rx).astype(f32))
+    rows = (hi[:, 1] - lo[:, 1] + 1) * (hi[:, 2] - lo[:, 2] + 1)
+    nx, ny, nz = g.dims
+    assert nx * ny * nz <= 1 << 24
+    c = g.cells(xyz)
+    cum = np.zeros((nx + 1, ny + 1, nz + 1), np.int64)  # cum[i, j, k]: points in cells below (i, j, k)
+    np.add.at(cum, (c[:, 0] + 1, c[:, 1] + 1, c[:, 2] + 1), 1)
+    cum = cum.cumsum(0).cumsum(1).cumsum(2)
+    a, b = lo, hi + 1
+    pts = np.zeros(len(xyz), np.int64)
+    for sx, ix in ((1, b[:, 0]), (-1, a[:, 0])):
+        for sy, iy in ((1, b[:, 1]), (-1, a[:, 1])):
+            for sz, iz in ((1, b[:, 2]), (-1, a[:, 2])):
+                pts += sx * sy * sz * cum[ix, iy, iz]
+    return rows, pts, float(rx) / g.h

@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 import boundary_cases as bc
+import normals_cases as nc
 from conftest import ROOT
 
 pytestmark = pytest.mark.gpu
@@ -127,6 +128,47 @@ def test_gap_and_flags_within_bound_of_the_truth(name):
           int((ref.decided & ~flag_ok).sum()))
     assert (err[gap_ok] <= bc.bound(ref.sens[gap_ok])).all()
     np.testing.assert_array_equal(flags[flag_ok], (ref.truth > np.float64(THR_F))[flag_ok])
+
+
+@pytest.mark.parametrize("name", tuple(nc.FAR_SHEET_X0))
+def test_far_sheet_by_both_routes(name):
+    """far_sheet with and without nn_indices: boundary_sorted_kernel and boundary_kernel, each with the
+    hand-off to boundary_wave_kernel for the queries that reach the ring cap.  At |X0| = 4096.5 the grid's slop
+    exceeds every k-th neighbour distance (test_far_frame_certificates), so ordinary queries of the dense sheet
+    may reach the cap while their neighbours are near; what share does cannot be certified from the CPU side
+    -- the boundary grid's cell edge is auto-sized and the call has no hand-off counter -- so nothing here
+    depends on it: the sets equal the reference's whichever path a query takes, and the call without the
+    indices gives the same gap bits (the gap depends on the set alone) within the bound of the truth.
+    Printed, not asserted: the pair_tests of the three calls and the boundary ms_device, for DESIGN.md's
+    account of what the slop costs a fine cloud in a far frame (the control is the same cloud at X0 = 0)."""
+    import fpfh_cases as fc
+
+    e = _engine()
+    xyz, nrm, k = bc.case(name)
+    ref = bc.case_reference(name)
+    gap_ok, flag_ok = bc.comparable(ref)
+    runs = {}
+    for want in (True, False):
+        flags, gap, nn, info = e.boundary_points(xyz, nrm, k, bc.THRESHOLD, want_gap=True, want_indices=want)
+        runs[want] = (flags, gap, info)
+        if want:
+            np.testing.assert_array_equal(nn, ref.nn)
+        else:
+            assert nn is None
+        np.testing.assert_array_equal(np.isnan(gap), ~ref.decided)
+        err = np.abs(gap.astype(np.float64) - ref.truth)
+        assert (err[gap_ok] <= bc.bound(ref.sens[gap_ok])).all()
+        np.testing.assert_array_equal(flags[flag_ok], (ref.truth > np.float64(THR_F))[flag_ok])
+        assert info["n_finite"] == len(xyz) and info["n_undecided"] == 0 and info["pair_tests"] >= ref.size.sum()
+    np.testing.assert_array_equal(_bits(runs[False][1]), _bits(runs[True][1]))
+    np.testing.assert_array_equal(runs[False][0], runs[True][0])
+    np.testing.assert_array_equal(_bits(runs[True][1]), _bits(_run(name)[1]))
+    ninfo = e.estimate_normals(*nc.case(name))[3]
+    finfo = e.fpfh_features(*fc.case(name))[3]
+    print(name, "pair_tests: normals", ninfo["pair_tests"], "boundary with indices", runs[True][2]["pair_tests"],
+          "without", runs[False][2]["pair_tests"], "fpfh", finfo["pair_tests"], "| ms_device: boundary with indices",
+          runs[True][2]["ms_device"], "without", runs[False][2]["ms_device"], "normals", ninfo["ms_device"], "fpfh",
+          finfo["ms_device"])
 
 
 def test_other_thresholds():

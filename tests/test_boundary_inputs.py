@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import boundary_cases as bc
+import normals_cases as nc
 from conftest import ROOT
 
 # the cases whose geometry allows interior and boundary records; at k = 7 six neighbours cannot close
@@ -51,7 +52,7 @@ def test_ties_at_the_kth_place(name):
     every other case's sets do not depend on the tie rule"""
     ref = bc.case_reference(name)
     print(name, "records with a tie at the k-th place", int(ref.tie.sum()))
-    if name in ("lattice", "pile"):
+    if name in bc.TIE_CASES:
         assert ref.tie.sum() >= 50
     else:
         assert ref.tie.sum() == 0
@@ -71,6 +72,9 @@ def test_regime_certificates():
     # lattice: more ties than places left -- the lowest-index rule decides the set
     ref = bc.case_reference("lattice")
     assert (ref.tie & (ref.n_le > 30)).sum() >= 50
+    # lattice_rim: the same in a frame of 2^-11 steps, where most records tie
+    ref = bc.case_reference("lattice_rim")
+    assert (ref.tie & (ref.n_le > 30)).sum() >= 50
     # clump: k = 32 fills the list without sentinels; the crowded disc puts 1500 points in a 2 cm spot
     xyz, _nrm, k = bc.case("clump")
     assert k == 32 and len(xyz) == 3100
@@ -81,6 +85,43 @@ def test_regime_certificates():
     far = np.abs(xyz).max(1) > 20
     assert far.sum() == 40 and np.isnan(nrm[far]).all() and np.isfinite(nrm[~far]).all()
     assert not bc.case_reference("outliers").decided[far].any()
+
+
+def _kth_distance(name):
+    xyz, _nrm, k = bc.case(name)
+    ref = bc.case_reference(name)
+    assert (ref.size == k).all()
+    return np.sqrt(bc.d2_f32(xyz, xyz[ref.nn[:, k - 1]]).astype(np.float64))
+
+
+def test_far_frame_certificates():
+    """far_sheet: the slop of any grid over the cloud (8 float steps of the largest coordinate, whatever the
+    cell edge) exceeds every record's k-th neighbour distance, so ring_search's bound L 0.99999 - slop proves
+    nothing until the unvisited cells are a slop farther than the k-th neighbour -- neighbours near, bounds
+    weak -- where the control at X0 = 0 has a slop below a thousandth of that distance.  How many queries then
+    reach the ring cap depends on the auto-sized cell edge, which the CPU side does not restate: the GPU tests
+    assert parity whichever path a query takes.  far_part: the same sets as a reference of the shifted cloud,
+    no ties; truth normals everywhere."""
+    for name in nc.FAR_SHEET_X0:
+        xyz, nrm, k = bc.case(name)
+        slop = 8.0 * float(np.abs(xyz).max()) * 2.0 ** -23
+        kth = _kth_distance(name)
+        print(name, "slop", slop, "k-th neighbour distance", float(kth.min()), "-", float(kth.max()))
+        assert k == bc.K_DEFAULT and np.isfinite(nrm).all() and bc.case_reference(name).decided.all()
+        if name == "far_sheet_origin":
+            assert slop < 1e-3 * kth.min()
+        else:
+            assert slop > kth.max() and slop > 3 * nc.FAR_SHEET_RADIUS
+        assert (np.abs(np.linalg.norm(nrm.astype(np.float64), axis=1) - 1) < 1e-6).all()
+    for name in nc.FAR_PART_OFFSET:
+        xyz, nrm, k = bc.case(name)
+        assert k == bc.K_DEFAULT and len(xyz) == 3000 and np.isfinite(nrm).all()
+        assert (nrm == bc.truth_normals(xyz, nc.case(name)[1])).all()
+        assert bc.case_reference(name).decided.all()
+    xyz, nrm, k = bc.case("lattice_rim")
+    assert k == bc.K_DEFAULT and (xyz == nc.lattice_rim()[0]).all() and np.isfinite(nrm).all()
+    ref = bc.case_reference("lattice_rim")
+    assert ref.tie.sum() * 2 >= len(xyz)  # ties are the norm: the (d2, original index) rule decides most sets
 
 
 def test_small_case_facts():

@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import boundary_cases as bc
 import fpfh_cases as fc
 import normals_cases as nc
 from cluster_edges_cases import d2_f32, r2_of
@@ -105,6 +106,52 @@ def test_cases_are_what_they_claim():
     for k in range(4):
         assert len(fc.case(f"n{k}")[0]) == k
     assert (fc.case_reference("n3").size == 3).all()
+
+
+def test_far_cases_are_what_they_claim():
+    assert fc.CLOUD_CASES + fc.EDGE_VALUE_CASES == fc.CASES and set(fc.FAR_CASES) <= set(fc.CLOUD_CASES)
+    assert not set(fc.EDGE_VALUE_CASES) & set(fc.CLOUD_CASES) and len(fc.CLOUD_CASES) == 9 + len(fc.FAR_CASES)
+    # far_sheet: the normals' radius, every fifth record a keypoint; at |X0| = 4096.5 the cell box of at least
+    # a third of the records -- of the keypoints (mark, final) and of the computed rows (SPFH) alike -- has
+    # more than 64 rows of cells: fpfh_walk's outer loop takes a second turn.  The control has no box above
+    # 4 x 4 rows.  Conditions on the inputs from the float32 restatement of the cell function
+    for name in nc.FAR_SHEET_X0:
+        xyz, nrm, kp, radius = fc.case(name)
+        ref = fc.case_reference(name)
+        assert radius == nc.FAR_SHEET_RADIUS and (kp == np.arange(0, 6000, 5)).all() and np.isfinite(nrm).all()
+        assert (xyz == nc.case(name)[0]).all() and (nrm == bc.case(name)[1]).all()
+        rows, _pts, rel = nc.box_facts(xyz, radius)
+        print(name, "rx / h", rel, "rows of a keypoint's box: above 64", int((rows[kp] > 64).sum()), "of", len(kp),
+              "of a computed row's", int((rows[ref.union] > 64).sum()), "of", int(ref.union.sum()), "max", int(rows.max()))
+        if name == "far_sheet_origin":
+            assert rows.max() <= 16
+        else:
+            assert (rows[kp] > 64).sum() * 3 >= len(kp) and (rows[ref.union] > 64).sum() * 3 >= ref.union.sum()
+            assert rows.max() > 64 and ref.size.max() <= 64  # many rows, few members: the rows are the load
+    # far_part: _part()'s recipe in the site frame -- truth normals, the truth boundary keypoints of that frame
+    for name, (which, factor) in fc.FAR_PART_CASES.items():
+        xyz, nrm, kp, radius = fc.case(name)
+        bref = bc.case_reference(which)
+        assert (xyz == nc.case(which)[0]).all() and (nrm == bc.case(which)[1]).all()
+        assert radius == factor * nc._far_part_base()[1] and nc.case(which)[1] == 10.0 * nc._far_part_base()[1]
+        with np.errstate(invalid="ignore"):
+            assert (kp == np.flatnonzero(bref.decided & (bref.truth > np.float64(np.float32(bc.THRESHOLD))))).all()
+        assert 300 <= len(kp) <= 2000 and np.isfinite(nrm[kp]).all()
+    # lattice_rim: sizes decided at the rim -- the reference's are the strict integer counts
+    from scipy.spatial import cKDTree
+
+    xyz, nrm, kp, radius = fc.case("lattice_rim")
+    ref = fc.case_reference("lattice_rim")
+    ij = nc.lattice_rim_ij()
+    pairs = cKDTree(ij).query_pairs(np.sqrt(25.5), output_type="ndarray")
+    d2i = ((ij[pairs[:, 0]] - ij[pairs[:, 1]]) ** 2).sum(1)
+    np.testing.assert_array_equal(ref.full_size, 1 + np.bincount(pairs[d2i < 25].ravel(), minlength=len(ij)))
+    assert float(r2_of(radius)) == 25 * nc.LATTICE_RIM_STEP ** 2 and (kp == np.arange(0, len(xyz), 5)).all()
+    at_rim = d2_f32(xyz[pairs[:, 0]], xyz[pairs[:, 1]]) == r2_of(radius)
+    assert (at_rim == (d2i == 25)).all() and at_rim.sum() >= 1000
+    # ordered pairs one float step of d2 below the rim (24 = 16 + 4 + 4 lattice steps squared): accepted
+    assert (ref.d2.astype(np.float64) == 24 * nc.LATTICE_RIM_STEP ** 2).sum() >= 2000
+    assert not (ref.d2 >= r2_of(radius)).any()
 
 
 @pytest.mark.parametrize("name", fc.CLOUD_CASES)

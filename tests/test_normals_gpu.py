@@ -91,7 +91,10 @@ def test_direction(name):
     assert ang.max() <= pcl_median
 
 
-@pytest.mark.parametrize("name,viewpoint", [(n, None) for n in nc.DIRECTION_CASES] + [("part", nc.VIEWPOINT)])
+@pytest.mark.parametrize(
+    "name,viewpoint", [(n, None) for n in nc.DIRECTION_CASES] + list(nc.viewpoints().items()),
+    # `part` keeps the id it had when it was the only case with a viewpoint of its own (the 8th parameter set)
+    ids=[f"{n}-None" for n in nc.DIRECTION_CASES] + ["part-viewpoint7" if n == "part" else f"{n}-viewpoint" for n in nc.viewpoints()])
 def test_sign(name, viewpoint):
     xyz, radius = nc.case(name)
     ref = nc.case_reference(name)

@@ -23,10 +23,18 @@ def test_few_records_are_excluded(name):
     low_gap = has & ~(ref.gap_rel >= nc.GAP_MIN)
     print(name, "records", len(xyz), "with a normal", int(has.sum()), "gap below", nc.GAP_MIN, int(low_gap.sum()))
     assert low_gap.sum() <= 0.01 * has.sum()
-    for vp in ((0.0, 0.0, 0.0),) + ((nc.VIEWPOINT,) if name == "part" else ()):
+    extra = nc.viewpoints()
+    for vp in ((0.0, 0.0, 0.0),) + ((extra[name],) if name in extra else ()):
         _sign, cos = nc.orientation(xyz, ref, vp)
         grazing = has & ~(cos >= nc.COS_MIN)
         print(name, "viewpoint", vp, "grazing", int(grazing.sum()))
+        if name == "far_sheet_origin" and vp == (0.0, 0.0, 0.0):
+            # the control's sheet x = 0.3 y - 0.2 z passes through the default viewpoint: every view direction
+            # lies in the plane up to the sheet's noise.  The cap holds at the case's own viewpoint (below);
+            # the sign test at the origin compares whatever COS_MIN leaves
+            plane = np.asarray(nc.FAR_SHEET_PLANE) / np.linalg.norm(nc.FAR_SHEET_PLANE)
+            assert np.abs(xyz.astype(np.float64) @ plane).max() < 1e-3 and name in extra
+            continue
         assert grazing.sum() <= 0.01 * has.sum()
 
 
@@ -79,6 +87,90 @@ def test_case_shapes():
     ref = nc.case_reference("nonfinite")
     assert bad.sum() == 50 and np.isnan(xyz).any() and np.isposinf(xyz).any() and np.isneginf(xyz).any()
     assert not ref.has[bad].any() and (ref.count[bad] == 0).all() and ref.has[~bad].sum() > 2000
+
+
+def test_far_sheet_regimes():
+    """far_sheet: the grid's slop exceeds the radius, so a single query's cell box (fpfh_box; a group's box in
+    normals_tile_kernel is at least as large) has more than 64 rows of cells and more points than one staged
+    chunk for at least a third of the records -- on both sides of the origin -- while the control, the same
+    draws at X0 = 0, has no box above 4 x 4 rows.  Conditions on the inputs, from the float32 restatement of
+    the cell function; nothing here measures the engine."""
+    ctrl, radius = nc.case("far_sheet_origin")
+    rows0, pts0, rel0 = nc.box_facts(ctrl, radius)
+    h, _most, dims = nc.grid_facts(ctrl, radius)
+    print("far_sheet_origin rx / h", rel0, "rows max", int(rows0.max()), "points max", int(pts0.max()), "dims", dims)
+    assert h == radius and rel0 < 1.001 and rows0.max() <= 16 and pts0.max() <= nc.STAGE_POINTS
+    for name in ("far_sheet", "far_sheet_neg"):
+        xyz, r = nc.case(name)
+        x0 = nc.FAR_SHEET_X0[name]
+        assert r == radius and len(xyz) == 6000 and len(np.unique(xyz, axis=0)) == 6000
+        # the same draws in another frame: y and z bit for bit, x within half a float step of X0 + the control's
+        assert (xyz[:, 1:] == ctrl[:, 1:]).all()
+        assert np.abs((xyz[:, 0].astype(np.float64) - x0) - ctrl[:, 0]).max() <= 2.0 ** -12 + 2.0 ** -30
+        assert np.sign(xyz[:, 0]).min() == np.sign(xyz[:, 0]).max() == np.sign(x0)
+        rows, pts, rel = nc.box_facts(xyz, r)
+        h, _most, dims = nc.grid_facts(xyz, r)
+        print(name, "rx / h", rel, "rows: share above 64", float((rows > 64).mean()), "max", int(rows.max()),
+              "points: share above", nc.STAGE_POINTS, float((pts > nc.STAGE_POINTS).mean()), "max", int(pts.max()),
+              "dims", dims)
+        assert h == r and rel > 4.0                                 # the slop alone is three cell edges
+        assert (rows > 64).sum() * 3 >= len(xyz)                    # fpfh_walk's second turn of 64 rows
+        assert (pts > nc.STAGE_POINTS).sum() * 3 >= len(xyz)        # more than one staged chunk per group
+        ref = nc.case_reference(name)
+        assert ref.has.all() and (ref.gap_rel >= nc.GAP_MIN).all()
+
+
+def test_far_part_is_the_part_shifted():
+    """far_part: the first 3000 records of the part's scan plus a site offset, added in float32; the offsets
+    are those of the geometry-edge tests; the non-default viewpoint moves with the cloud"""
+    from geometry_edges_cases import OFFSETS
+
+    scan, _res = nc._part_scan()
+    for name, site in nc.FAR_PART_OFFSET.items():
+        xyz, radius = nc.case(name)
+        off = np.asarray(OFFSETS[site], np.float32)
+        assert np.abs(off).max() >= 300 and (xyz == scan[:3000] + off).all() and xyz.dtype == np.float32
+        assert radius == 10.0 * nc.resolution(scan[:3000])
+        assert nc.viewpoints()[name] == tuple((np.asarray(nc.VIEWPOINT, np.float32) + off).tolist())
+        ref = nc.case_reference(name)
+        assert ref.has.all() and (ref.gap_rel >= nc.GAP_MIN).all()
+        assert np.linalg.norm(xyz.astype(np.float64), axis=1).min() > 300  # the default viewpoint is far away
+
+
+def test_lattice_rim_pairs_are_exact():
+    """lattice_rim: every float d2 is the integer lattice d2 times 2^-22 exactly, float(radius^2) is 25 of
+    them, and thousands of pairs sit at d2 == r2 (rejected) and one float step below (24: accepted) -- the
+    sets are decided by the strictness of the test alone.  The reference's counts are the integer counts."""
+    from scipy.spatial import cKDTree
+
+    xyz, radius = nc.case("lattice_rim")
+    ij = nc.lattice_rim_ij()
+    step = nc.LATTICE_RIM_STEP
+    assert len(np.unique(ij, axis=0)) == len(ij) == len(xyz) >= 5000
+    assert (xyz.astype(np.float64) == np.asarray(nc.LATTICE_RIM_OFF) + ij * step).all()
+    mag = np.abs(xyz)
+    assert ((mag >= 4096) & (mag < 8192)).all()  # one binade: the float step is 2^-11 for every coordinate
+    assert (np.abs(np.nextafter(xyz, np.float32(np.inf)) - xyz) == np.float32(step)).all()
+    r2 = nc.r2_of(radius)
+    assert float(r2) == 25 * step * step
+    pairs = cKDTree(ij).query_pairs(np.sqrt(40.5), output_type="ndarray")  # every pair with an integer d2 <= 40
+    a, b = pairs[:, 0], pairs[:, 1]
+    d2i = ((ij[a] - ij[b]) ** 2).sum(1)
+    assert (nc.d2_f32(xyz[a], xyz[b]).astype(np.float64) == d2i * (step * step)).all()
+    assert (nc.d2_f32(xyz[b], xyz[a]).astype(np.float64) == d2i * (step * step)).all()
+    at_rim, below = int((d2i == 25).sum()), int((d2i == 24).sum())
+    rim_records = int((np.bincount(pairs[d2i == 25].ravel(), minlength=len(ij)) > 0).sum())
+    print("lattice_rim records", len(xyz), "pairs at d2 == r2", at_rim, "one step below", below, "accepted",
+          int((d2i < 25).sum()), "records with a pair at the rim", rim_records)
+    assert at_rim >= 1000 and below >= 1000
+    assert not ((d2i > 24) & (d2i < 25)).any()  # integers: nothing between the last accepted and the rim
+    ref = nc.case_reference("lattice_rim")
+    np.testing.assert_array_equal(ref.count, 1 + np.bincount(pairs[d2i < 25].ravel(), minlength=len(ij)))
+    # slop over radius: the box is three cells wide on either side (the grid: cells of one radius)
+    _rows, _pts, rel = nc.box_facts(xyz, radius)
+    h, _most, dims = nc.grid_facts(xyz, radius)
+    print("lattice_rim rx / h", rel, "dims", dims)
+    assert h == radius and 2.5 < rel < 3.5
 
 
 def test_degenerate_and_edge_clouds():
