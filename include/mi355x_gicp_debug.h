@@ -107,13 +107,31 @@ int mgicp_debug_target_cov_slice(mgicp_ctx* ctx, int nranks, int rank, double* o
  * entries, out[4] reject cells, out[5] overflow cells, out[6] pool entries used, out[7] fine-grid
  * cells (0 when the lists are off: debug option "vlist" 0 or a gate too wide for a fine grid) */
 int mgicp_debug_vlist_stats(mgicp_ctx* ctx, long long out[8]);
+/* the fine grid of those lists, its counters and (optionally) every fine cell, computed on the host from
+ * copies of the state words, the counters and the long lists' header entries (no kernel runs):
+ * out[0..2] grid origin ox oy oz, out[3] cell edge c, out[4] es (growth of a cell's box covering the fp32
+ * cell assignment), out[5..7] nx ny nz, out[8] the gate, out[9] the target grid's cell edge h, out[10] 1
+ * when the gate is too wide for a fine grid (lists off: out[0..7] and all that follows are 0), out[11]
+ * pool capacity and out[12] pool head (entries; the head may pass the capacity, no list lies beyond it),
+ * out[13] slots of the build list, out[14] cells requested, out[15] queries pending and out[16] cells
+ * handed to the build's second pass by the last sweep, out[17] fine-grid cells (cell i = ix + nx (iy +
+ * ny iz)), out[18] 1 once the state words and the pool are allocated (else out[11..16] are 0 and no cell
+ * is written), out[19] the float reciprocal of c the queries' cell assignment multiplies by, out[20..23]
+ * 0.  state / length / offset (each optional, `cap` >= out[17] elements): per fine cell its class (0 not
+ * built, 1 touched, 2 requested, 3 reject, 4 overflow, 5 listed), its list's true length (a long list's
+ * from its header entry) and the list's first pool entry (a long list's header; the list occupies
+ * length rounded up to a multiple of 4, + 4 for a long list's header). */
+int mgicp_debug_vlist_layout(mgicp_ctx* ctx, double out[24], uint8_t* state, uint32_t* length, uint32_t* offset,
+                             size_t cap);
 /* enable (1) / disable (0) per-launch HIP event timing (off by default); objective passes
  * ([2]) are sampled every 8th launch, every other family is timed on every launch */
 int mgicp_set_profiling(mgicp_ctx* ctx, int on);
 /* test / diagnostic forms of the engine, set explicitly on one context (never through the
  * environment): "resident", "host_rows", "srv_cus", "fused_finish", "gated", "bar_cmd" (the
  * objective-pass path), "async_cov", "lazy_src_cov", "knn_logged", "knn_wave" (covariances), "vlist",
- * "vlist_cold", "vlist_eager", "vlist_stats", "fuse_compact" (1-NN cell lists),
+ * "vlist_cold", "vlist_eager", "vlist_stats", "vlist_pool" (a list pool of max(N, 4096) entries instead of
+ * the default max(2^22, 32 n); 0: the default; such a context leaves no lists in the target cache),
+ * "fuse_compact" (1-NN cell lists),
  * "target_cache".  Every form gives the default path's results bit for bit (the GPU tests
  * that pin each one: INTEGRATION.md "Debug options"); MGICP_E_INVALID for an unknown name. */
 int mgicp_debug_option(mgicp_ctx* ctx, const char* name, double value);

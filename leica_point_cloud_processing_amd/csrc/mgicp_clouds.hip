@@ -335,7 +335,8 @@ void mgicp::tcache_donate(mgicp_ctx* ctx, bool cov_complete) {
   // the cell lists travel with the target once built (the donor ran 3+ aligns on it).  The list policy
   // itself does not go on across contexts: GICPState's engines run 2 aligns each, and building the lists
   // in a later cycle cost 39 + 151 ms at C4 (profiles/r05/check5) against ~1.6 ms saved per cycle
-  c.vl_valid = ctx->vl_valid && ctx->vl_alloc;
+  // (not from a context with a test-sized pool, debug option "vlist_pool": an adopter would inherit its cap)
+  c.vl_valid = ctx->vl_valid && ctx->vl_alloc && ctx->vl_pool_entries == 0;
   if (c.vl_valid) swap_list_state(c, *ctx);
   c.valid = true;
   c.donations++;

@@ -385,6 +385,7 @@ struct mgicp_ctx {
   // eagerly or ~15 ms spread over two aligns lazily at C4, so the reference's align + iterate pair on
   // one cloud pair (GICPAlignment.cpp:96, :116) runs both aligns without them (r04, profiles/r04/policy)
   int vl_cold_groups = 2;
+  size_t vl_pool_entries = 0;         // debug option "vlist_pool" N: a pool of max(N, 4096) entries (0: the default size)
   // r05 target cache (process-wide, one entry per device): a destroyed context leaves its target's grid,
   // covariances and 1-NN cell lists there; a later context whose set_target uploads the same points
   // (compared on the device, bit for bit) adopts them instead of rebuilding -- GICPState constructs a

@@ -90,6 +90,75 @@ int mgicp_debug_vlist_stats(mgicp_ctx* ctx, long long out[8]) {
   return MGICP_OK;
 }
 
+// The fine grid's layout, the list counters and (state / length / offset non-null) every fine cell's
+// state class, true list length and pool offset: host work over device-to-host copies of the state
+// words, the counters and the long lists' header entries (4 bytes each); no kernel.
+int mgicp_debug_vlist_layout(mgicp_ctx* ctx, double out[24], uint8_t* state, uint32_t* length, uint32_t* offset,
+                             size_t cap) {
+  if (!ctx || !out) return MGICP_E_INVALID;
+  for (int i = 0; i < 24; ++i) out[i] = 0.0;
+  out[8] = ctx->prm.max_corr_dist;
+  out[9] = ctx->tgt.view.h;
+  if (!ctx->vlist || !ctx->vl_valid) return MGICP_OK;
+  const VListView& v = ctx->vl;
+  out[8] = v.gate;
+  out[10] = ctx->vl_off ? 1.0 : 0.0;
+  if (ctx->vl_off) return MGICP_OK;
+  out[0] = v.ox; out[1] = v.oy; out[2] = v.oz;
+  out[3] = v.c;
+  out[4] = v.es;
+  out[5] = v.nx; out[6] = v.ny; out[7] = v.nz;
+  out[17] = static_cast<double>(ctx->vl_ncells);
+  out[19] = v.inv_c;
+  if (!ctx->vl_alloc) return MGICP_OK;
+  out[18] = 1.0;
+  HIPCK(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  unsigned int c8[8];
+  HIPCK(hipMemcpyAsync(c8, ctx->vl_ctr.p, sizeof(c8), hipMemcpyDeviceToHost, s));
+  int rc = sync(ctx);
+  if (rc) return rc;
+  out[11] = v.pool_cap;
+  out[12] = c8[0];
+  out[13] = v.build_cap;
+  out[14] = c8[1];
+  out[15] = c8[2];
+  out[16] = c8[4];
+  if (!state && !length && !offset) return MGICP_OK;
+  const size_t nc = ctx->vl_ncells;
+  if (cap < nc) return fail(ctx, MGICP_E_INVALID, "debug_vlist_layout: cap below the fine grid's cell count");
+  std::vector<uint32_t> cell(nc);
+  HIPCK(hipMemcpyAsync(cell.data(), ctx->vl_cell.p, nc * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  if ((rc = sync(ctx))) return rc;
+  std::vector<size_t> lng;  // the long lists' cells: their true counts are in the pool (header entry, x bits)
+  for (size_t i = 0; i < nc; ++i) {
+    const uint32_t c = cell[i];
+    uint8_t st = 5;
+    uint32_t len = 0, off = 0;
+    if (c == kVlNotBuilt) st = 0;
+    else if (c == kVlRequested) st = 2;
+    else if (c == kVlOverflow) st = 4;
+    else if (c == kVlReject) st = 3;
+    else if (c >= kVlTouched) st = 1;
+    else {
+      off = (c >> 6) << 2;
+      len = c & 63u;
+      if (len == static_cast<uint32_t>(kVlLong)) {
+        if (off >= v.pool_cap) return fail(ctx, MGICP_E_HIP, "debug_vlist_layout: a long list starts past the pool");
+        if (length) lng.push_back(i);
+      }
+    }
+    if (state) state[i] = st;
+    if (length) length[i] = len;
+    if (offset) offset[i] = off;
+  }
+  // one 4-byte copy per long list (its header's count), not the pool
+  for (size_t i : lng)
+    HIPCK(hipMemcpyAsync(&length[i], &ctx->vl_pool.p[(cell[i] >> 6) << 2].x, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  if (!lng.empty() && (rc = sync(ctx))) return rc;
+  return MGICP_OK;
+}
+
 // r06: the objective's stream order -- original indices of this rank's source points in the order the
 // compacted streams (and so every sum's fixed tree) visit them; the oracle's summation-order ledger runs
 // the engine's tree over it (oracle/gicp_ref.c ref_set_sum_order).  Returns the count (<= cap written).
@@ -467,7 +536,10 @@ int mgicp_debug_option(mgicp_ctx* ctx, const char* name, double value) {
   } else if (n == "vlist") ctx->vlist = on, ctx->vl_valid = false;  // the target's 1-NN cell lists
   else if (n == "vlist_cold") ctx->vl_cold_groups = std::max(0, iv), ctx->vl_valid = false;
   else if (n == "vlist_eager") ctx->vl_eager = on, ctx->vl_valid = false;
-  else if (n == "vlist_stats") ctx->vl_stats = on;      // per-sweep list statistics on stderr
+  else if (n == "vlist_pool") {                         // list pool of max(N, 4096) entries (0: the default size)
+    ctx->vl_pool_entries = value >= 1.0 ? static_cast<size_t>(std::min(value, 134217728.0)) : 0;
+    ctx->vl_valid = false;
+  } else if (n == "vlist_stats") ctx->vl_stats = on;    // per-sweep list statistics on stderr
   else if (n == "fuse_compact") ctx->fuse_compact = on; // compaction fused into listed sweeps
   else if (n == "target_cache") ctx->tcache_on = on;    // adopt / leave the target state (process cache)
   else if (n == "bar_cmd") {                            // server commands through the BAR (else pinned copy)

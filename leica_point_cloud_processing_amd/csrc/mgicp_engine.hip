@@ -74,18 +74,22 @@ int vl_prepare(mgicp_ctx* ctx) {
     constexpr size_t kVlMaxCells = size_t(1) << 28;
     int nd[3] = {0, 0, 0};
     double pad = 0;
-    for (int it = 0; it < 64; ++it) {
+    // (the cell counts in double: PCL's default gate, sqrt(DBL_MAX), is far outside an int or a size_t;
+    // such a gate leaves the loop with c past 4 h, or not a number, and the lists are off)
+    const double c_max = 4.0 * std::max(h, 1e-6);
+    for (int it = 0; it < 64 && c <= c_max; ++it) {
       pad = gate * (1.0 + 1e-5) + 1e-9 + 2.0 * c;
-      size_t nc = 1;
+      double nc = 1.0;
       for (int d = 0; d < 3; ++d) {
-        nd[d] = static_cast<int>(std::floor((static_cast<double>(t.hi[d] - t.lo[d]) + 2.0 * pad) / c)) + 1;
-        nc *= static_cast<size_t>(nd[d]);
+        const double m = std::floor((static_cast<double>(t.hi[d] - t.lo[d]) + 2.0 * pad) / c) + 1.0;
+        nd[d] = m < 2147483647.0 ? static_cast<int>(m) : 2147483647;
+        nc *= m;
       }
-      if (nc <= kVlMaxCells) break;
-      c *= std::cbrt(static_cast<double>(nc) / kVlMaxCells) * 1.01;
+      if (nc <= static_cast<double>(kVlMaxCells)) break;
+      c *= std::cbrt(nc / static_cast<double>(kVlMaxCells)) * 1.01;
     }
     ctx->vl.gate = gate;
-    if (c > 4.0 * std::max(h, 1e-6)) {  // a gate this wide against this target: lists would overflow
+    if (!(c <= c_max)) {  // a gate this wide against this target: lists would overflow
       ctx->vl_off = true;
       ctx->vl_valid = true;
       return MGICP_OK;
@@ -118,7 +122,10 @@ int vl_prepare(mgicp_ctx* ctx) {
     HIPCK(ctx->vl_cell.reserve(nc));
     HIPCK(hipMemsetAsync(ctx->vl_cell.p, 0xff, nc * sizeof(uint32_t), ctx->stream));
     // list starts are stored in units of 4 entries in 25 bits: at most 2^27 entries (16 bytes each)
-    const size_t cap = std::min<size_t>(size_t(1) << 27, std::max<size_t>(size_t(1) << 22, 32 * t.n));
+    // (debug option "vlist_pool": a small pool, so that tests reach the pool-full branch of the build)
+    const size_t want = ctx->vl_pool_entries ? std::max<size_t>(ctx->vl_pool_entries, 4096)
+                                             : std::max<size_t>(size_t(1) << 22, 32 * t.n);
+    const size_t cap = std::min<size_t>(size_t(1) << 27, want);
     HIPCK(ctx->vl_pool.reserve(cap));
     HIPCK(ctx->vl_ctr.reserve(8));  // [4]: the build's second-pass cells (r06)
     HIPCK(hipMemsetAsync(ctx->vl_ctr.p, 0, 8 * sizeof(unsigned int), ctx->stream));

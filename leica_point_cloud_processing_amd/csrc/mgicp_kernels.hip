@@ -2293,10 +2293,11 @@ __global__ __launch_bounds__(256) void vl_fallback_kernel(GridView tg, VListView
   }
 }
 
-// diagnostics: [0] cells listed [1] list entries [2] reject [3] overflow [4] requested [5] not built,
-// [8 + L] cells with list length L (L < 56)
+// diagnostics: [0] cells listed [1] list entries (a long list's true count, from its header) [2] reject
+// [3] overflow [4] requested [5] touched (not-built cells are not counted), [8 + L] cells with list length L
+// (55: that or more)
 __global__ __launch_bounds__(256) void vl_stats_kernel(const uint32_t* __restrict__ cell, size_t n,
-                                                       unsigned long long* out) {
+                                                       const float4* __restrict__ pool, unsigned long long* out) {
   // r06: per-block LDS counts, one atomic per block and counter (r05: one global atomic per listed cell on
   // 64 shared addresses, 23 ms per call at C4)
   __shared__ unsigned int cnt[64];
@@ -2309,8 +2310,9 @@ __global__ __launch_bounds__(256) void vl_stats_kernel(const uint32_t* __restric
     if (c == kVlNotBuilt) continue;  // the common case: no atomics
     if (c < kVlTouched) {
       atomicAdd(&cnt[0], 1u);
-      entries += c & 63u;
-      atomicAdd(&cnt[8 + min(c & 63u, 55u)], 1u);
+      const uint32_t len = (c & 63u) == static_cast<uint32_t>(kVlLong) ? __float_as_uint(pool[(c >> 6) << 2].x) : c & 63u;
+      entries += len;
+      atomicAdd(&cnt[8 + min(len, 55u)], 1u);
     } else {
       atomicAdd(&cnt[c == kVlReject ? 2 : c == kVlOverflow ? 3 : c == kVlRequested ? 4 : 5], 1u);
     }
@@ -4656,7 +4658,7 @@ hipError_t launch_cov_need(const uint32_t* flags, uint8_t* cov_ok, size_t p0, si
 hipError_t launch_vl_stats(const VListView& vl, size_t ncells, unsigned long long* out, hipStream_t s) {
   hipError_t e = hipMemsetAsync(out, 0, 64 * sizeof(unsigned long long), s);
   if (e != hipSuccess) return e;
-  vl_stats_kernel<<<2048, 256, 0, s>>>(vl.cell, ncells, out);
+  vl_stats_kernel<<<2048, 256, 0, s>>>(vl.cell, ncells, vl.pool, out);
   return hipGetLastError();
 }
 

@@ -427,6 +427,37 @@ class GICPEngine:
         self._check(self._lib.mgicp_debug_vlist_stats(self._h, out), "vlist_stats")
         return {k: int(out[i]) for i, k in enumerate(self.VLIST_STATS)}
 
+    VLIST_LAYOUT = ("ox", "oy", "oz", "c", "es", "nx", "ny", "nz", "gate", "h", "vl_off", "pool_cap", "pool_head",
+                    "build_cap", "requested", "pending", "second_pass", "cells", "allocated", "inv_c")
+    VLIST_STATES = ("not_built", "touched", "requested", "reject", "overflow", "listed")
+
+    def vlist_layout(self, cells: bool = False):
+        """The fine grid of the 1-NN cell lists and its counters (mgicp_debug_vlist_layout) as a dict; with
+        cells = True also (state, length, offset): per fine cell its class (index into VLIST_STATES), its
+        list's true length and first pool entry (None when nothing is allocated).  cells = "state": the
+        classes alone, (state, None, None) -- one byte per cell, for grids of 2^28 cells."""
+        out = np.zeros(24, np.float64)
+        self._check(self._lib.mgicp_debug_vlist_layout(self._h, _dp(out), None, None, None, 0), "vlist_layout")
+        ints = ("nx", "ny", "nz", "vl_off", "pool_cap", "pool_head", "build_cap", "requested", "pending",
+                "second_pass", "cells", "allocated")
+        lay = {k: (int(out[i]) if k in ints else float(out[i])) for i, k in enumerate(self.VLIST_LAYOUT)}
+        if not cells:
+            return lay
+        if not lay["allocated"]:
+            return lay, None
+        n = lay["cells"]
+        state = np.zeros(n, np.uint8)
+        length = offset = None
+        if cells != "state":
+            length = np.zeros(n, np.uint32)
+            offset = np.zeros(n, np.uint32)
+        self._check(self._lib.mgicp_debug_vlist_layout(
+            self._h, _dp(out), state.ctypes.data, None if length is None else length.ctypes.data,
+            None if offset is None else offset.ctypes.data, n), "vlist_layout")
+        for i, k in enumerate(self.VLIST_LAYOUT):
+            lay[k] = int(out[i]) if k in ints else float(out[i])
+        return lay, (state, length, offset)
+
     # -- introspection (parity tests, profiling) ----------------------------------------------
     def debug_source_order(self, n: int) -> np.ndarray:
         """Original indices of the source points in the objective's stream order (mgicp_debug_source_order)."""
