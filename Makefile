@@ -12,7 +12,7 @@ LDMAP := -Wl,--version-script=$(MAP)
 # -ffp-contract=off: no FMA contraction, so fp32/fp64 expressions round like PCL's SSE2 Eigen
 HIPFLAGS := -O3 -std=c++17 --offload-arch=$(ARCH) -fPIC -ffp-contract=off -Wall -Wno-unused-result
 
-all: $(LIB) oracle adapter-example adapter-replay fod-replay normals-replay boundary-replay fpfh-replay
+all: $(LIB) oracle adapter-example adapter-replay fod-replay normals-replay boundary-replay fpfh-replay corr-replay
 
 OBJDIR := $(PKG)/csrc/build
 OBJS  := $(OBJDIR)/mgicp_kernels.o $(OBJDIR)/mgicp_engine.o $(OBJDIR)/mgicp_clouds.o $(OBJDIR)/mgicp_pass.o \
@@ -113,6 +113,22 @@ $(FPFHREPLAY): adapter/InitialAlignment_features_mi355x.cpp include/mi355x_gicp.
 
 fpfh-replay: $(FPFHREPLAY)
 
+# adapter/InitialAlignment_correspondences_mi355x.cpp (InitialAlignment::obtainCorrespondences) compiled the
+# same way: the InitialAlignment.h of tests/adapter_standins_corr in front (the class with that private
+# member, its feature clouds and a pcl::Correspondence with PCL's virtual destructor), linked with a driver
+# that calls it on two feature files (test infrastructure)
+STANDIN_CORR := tests/adapter_standins_corr
+CORRREPLAY   := adapter/build/replay_test_correspondences
+$(CORRREPLAY): adapter/InitialAlignment_correspondences_mi355x.cpp include/mi355x_gicp.h $(wildcard $(STANDIN)/*.h) \
+               $(wildcard $(STANDIN_NRM)/*.h) $(wildcard $(STANDIN_CORR)/*.h) $(STANDIN)/Utils_standin.cpp \
+               $(STANDIN_CORR)/replay_test_correspondences.cpp $(LIB)
+	mkdir -p adapter/build
+	g++ -O2 -std=c++14 -Wall -Wextra -Werror -I$(STANDIN_CORR) -I$(STANDIN_NRM) -I$(STANDIN) -Iadapter -Iinclude -o $@ \
+	    adapter/InitialAlignment_correspondences_mi355x.cpp $(STANDIN)/Utils_standin.cpp \
+	    $(STANDIN_CORR)/replay_test_correspondences.cpp -L$(PKG) -lmgicp -Wl,-rpath,'$$ORIGIN/../../$(PKG)'
+
+corr-replay: $(CORRREPLAY)
+
 oracle:
 	$(MAKE) -C oracle
 
@@ -120,4 +136,4 @@ clean:
 	rm -f $(LIB) $(PKG)/libmgicp_*.so $(OBJS)
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle clean adapter-example adapter-replay fod-replay normals-replay boundary-replay fpfh-replay variant
+.PHONY: all oracle clean adapter-example adapter-replay fod-replay normals-replay boundary-replay fpfh-replay corr-replay variant

@@ -278,6 +278,53 @@ int mgicp_fpfh_features(mgicp_ctx* ctx, const float* xyz, size_t n, size_t strid
                         int* spfh_sizes /* may be NULL; n */,
                         mgicp_fpfh_info* info /* may be NULL */);
 
+/* InitialAlignment::obtainCorrespondences (src/InitialAlignment.cpp:510-517; every keypoint method calls it
+ * on the two feature clouds): pcl::registration::CorrespondenceEstimation<FPFHSignature33, FPFHSignature33>
+ * ::determineCorrespondences -- PCL 1.8.1 correspondence_estimation.hpp, KdTreeFLANN with
+ * flann::L2_Simple<float> and DefaultPointRepresentation<FPFHSignature33> restated [PCL].  PCL is not
+ * available to this project's tests, so parity with PCL binaries is unpinned (README "Parity"); the rules
+ * below are the contract, and every deviation from PCL in them is deliberate.
+ * Records: 33 floats at the start of records of source_stride_bytes / target_stride_bytes (>= 132, a
+ * multiple of 4; 132 = pcl::FPFHSignature33); other bytes are never read as data.
+ * Searched set: the target records whose 33 floats are all finite (KdTreeFLANN::convertCloudToArray drops
+ * the others and keeps the original indices); match holds original target record indices.
+ * Distance: d2(s, t) is a float that starts at 0.0f and takes the bins 0 .. 32 in ascending order, each step
+ * diff = s[b] - t[b]; d2 = d2 + diff * diff, without FMA contraction: the product is rounded, then the sum
+ * (L2_Simple's loop as x86-64 compiles it).
+ * Winner of a source record: among the searched targets with d2 < FLT_MAX (strict: FLANN's result set
+ * starts at FLT_MAX) the one with the smallest d2; equal d2 go to the lowest target record index -- the
+ * engine's rule; FLANN's choice among equal distances depends on its tree and is not reproduced.
+ * Rejection: a source record is dropped when (double)d2 > max_distance * max_distance, in double as PCL
+ * evaluates it; DBL_MAX (the reference's call) squares to +inf and rejects nothing.
+ * No correspondence (match = -1, distance = NaN): a dropped source record; one with no searched target or
+ * with no d2 below FLT_MAX; and, deviation (a), a source record with a non-finite value -- in PCL it trips
+ * an assert that release builds compile out and then searches with NaN.
+ * distance[i] = the winner's d2 (squared L2, as pcl::Correspondence::distance holds it).
+ * *n_correspondences = the matches >= 0; PCL's output is those, in ascending source index.
+ * MGICP_E_INVALID: a bad pointer or stride, a negative or NaN max_distance, n_source or n_target above
+ * INT32_MAX.  n_source = 0: OK; n_target = 0: OK, every match -1.
+ * Exact brute force on the device, split over launches of bounded work (DESIGN.md "Feature
+ * correspondences").  The same bits in every output on every call.
+ * Uses no cloud slot: a set source / target and their cached state stay as they are.
+ * Single rank: with a communicator attached it runs locally, without a collective. */
+typedef struct {
+    double n_source_valid;    /* source records with 33 finite values */
+    double n_target_valid;    /* target records with 33 finite values (the searched set) */
+    double n_correspondences; /* source records that got a match */
+    double n_tied;            /* matched source records whose minimum is attained by more than one valid target */
+    double pair_tests;        /* (source, target) distance evaluations the device began */
+    double ms_device;         /* first launch -> stream synchronise after the last */
+    double ms_total;          /* host call -> outputs written */
+} mgicp_match_info;
+int mgicp_match_features(mgicp_ctx* ctx,
+                         const float* source, size_t n_source, size_t source_stride_bytes, /* >= 132, multiple of 4 */
+                         const float* target, size_t n_target, size_t target_stride_bytes,
+                         double max_distance,          /* PCL's argument; DBL_MAX = the reference's call */
+                         int* match,                   /* n_source: target record index, -1 = none */
+                         float* distance,              /* may be NULL; n_source: squared L2, NaN where match = -1 */
+                         size_t* n_correspondences,    /* may be NULL */
+                         mgicp_match_info* info        /* may be NULL */);
+
 /* ---- the FOD-side callers either side of the GICP path ----
  * pcl::SegmentDifferences<PointXYZRGB>::segment as called by Filter::removeFromCloud
  * (src/Filter.cpp:176-189) on the cloud the FSM just transformed with

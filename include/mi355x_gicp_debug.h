@@ -123,6 +123,11 @@ int mgicp_debug_vlist_stats(mgicp_ctx* ctx, long long out[8]);
  * length rounded up to a multiple of 4, + 4 for a long list's header). */
 int mgicp_debug_vlist_layout(mgicp_ctx* ctx, double out[24], uint8_t* state, uint32_t* length, uint32_t* offset,
                              size_t cap);
+/* the last mgicp_match_features call on this context (DESIGN.md "Feature correspondences"): out[0] pairs
+ * begun, out[1..3] pairs left at the wave votes after bins 8, 16 and 24, out[4] launches of the match
+ * kernel, out[5] target rows of a launch, out[6] blocks that share them and out[7] target rows of each
+ * such block (the layout of the first launch); all 0 when the call ran no kernel */
+int mgicp_debug_match_stats(mgicp_ctx* ctx, long long out[8]);
 /* enable (1) / disable (0) per-launch HIP event timing (off by default); objective passes
  * ([2]) are sampled every 8th launch, every other family is timed on every launch */
 int mgicp_set_profiling(mgicp_ctx* ctx, int on);
@@ -132,7 +137,8 @@ int mgicp_set_profiling(mgicp_ctx* ctx, int on);
  * "vlist_cold", "vlist_eager", "vlist_stats", "vlist_pool" (a list pool of max(N, 4096) entries instead of
  * the default max(2^22, 32 n); 0: the default; such a context leaves no lists in the target cache),
  * "fuse_compact" (1-NN cell lists),
- * "target_cache".  Every form gives the default path's results bit for bit (the GPU tests
+ * "target_cache", "match_pairs_per_launch" (mgicp_match_features: the (source, target) pairs of one launch;
+ * 0: the default).  Every form gives the default path's results bit for bit (the GPU tests
  * that pin each one: INTEGRATION.md "Debug options"); MGICP_E_INVALID for an unknown name. */
 int mgicp_debug_option(mgicp_ctx* ctx, const char* name, double value);
 /* target cache (mgicp_release_cache): out[0] the current target was adopted from the cache, out[1]

@@ -105,6 +105,18 @@ class MgicpFpfhInfo(ctypes.Structure):
     ]
 
 
+class MgicpMatchInfo(ctypes.Structure):
+    _fields_ = [
+        ("n_source_valid", ctypes.c_double),
+        ("n_target_valid", ctypes.c_double),
+        ("n_correspondences", ctypes.c_double),
+        ("n_tied", ctypes.c_double),
+        ("pair_tests", ctypes.c_double),
+        ("ms_device", ctypes.c_double),
+        ("ms_total", ctypes.c_double),
+    ]
+
+
 class MgicpError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"mgicp error {code}: {msg}")
@@ -140,6 +152,8 @@ _SIGNATURES = {
                                               ctypes.POINTER(MgicpBoundaryInfo)]),
     "mgicp_fpfh_features": (ctypes.c_int, [_P, _P, _SZ, _SZ, _P, _SZ, _P, _SZ, ctypes.c_double, _P, _SZ, _P, _P,
                                             ctypes.POINTER(MgicpFpfhInfo)]),
+    "mgicp_match_features": (ctypes.c_int, [_P, _P, _SZ, _SZ, _P, _SZ, _SZ, ctypes.c_double, _P, _P,
+                                             ctypes.POINTER(_SZ), ctypes.POINTER(MgicpMatchInfo)]),
     "mgicp_segment_differences": (ctypes.c_int, [_P, _FP, _P, _SZ, _SZ, _P, _SZ, _SZ, ctypes.c_double, _P,
                                                   ctypes.POINTER(_SZ)]),
     "mgicp_voxel_grid": (ctypes.c_int, [_P, _P, _SZ, _SZ, ctypes.c_int, _DP, ctypes.c_int, _P, _SZ,
@@ -155,6 +169,7 @@ _SIGNATURES = {
                                                ctypes.POINTER(ctypes.c_longlong), ctypes.c_int]),
     "mgicp_debug_target_cov_slice": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _DP]),
     "mgicp_debug_vlist_stats": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_longlong)]),
+    "mgicp_debug_match_stats": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_longlong)]),
     "mgicp_debug_vlist_layout": (ctypes.c_int, [_P, _DP, _P, _P, _P, _SZ]),
     "mgicp_debug_source_order": (ctypes.c_int, [_P, ctypes.c_void_p, ctypes.c_size_t]),
     "mgicp_debug_covariances": (ctypes.c_int, [_P, ctypes.c_int, _DP]),

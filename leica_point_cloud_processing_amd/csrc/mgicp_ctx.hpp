@@ -358,6 +358,10 @@ struct mgicp_ctx {
   DevBuf<uint32_t> knn_fb;          // points the logged k-NN kernel leaves to the register-list one
   unsigned int knn_fallbacks = 0;   // their count in the last covariance launch
   DevBuf<float> fpartial;
+  // mgicp_match_features: pairs of one launch (debug option "match_pairs_per_launch") and the last call's
+  // figures for mgicp_debug_match_stats
+  unsigned long long match_pairs_per_launch = kMatchPairsPerLaunch;
+  long long match_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   // the target's 1-NN cell lists (r04, DESIGN.md "1-NN cell lists"; debug option "vlist" 0: the r03 sweeps)
   bool vlist = true;
   bool fuse_compact = true;           // r04: compaction fused into listed sweeps (debug option "fuse_compact")

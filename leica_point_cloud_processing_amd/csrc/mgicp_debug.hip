@@ -505,6 +505,12 @@ int mgicp_debug_cache_stats(mgicp_ctx* ctx, long long out[5]) {
   return MGICP_OK;
 }
 
+int mgicp_debug_match_stats(mgicp_ctx* ctx, long long out[8]) {
+  if (!ctx || !out) return MGICP_E_INVALID;
+  std::copy(ctx->match_stats, ctx->match_stats + 8, out);
+  return MGICP_OK;
+}
+
 // Test / diagnostic forms of the engine (INTEGRATION.md "Debug options"): explicit per-context calls,
 // never environment variables, so a deployment cannot switch a kernel by accident.
 // Pending covariance launches are joined and the stream drained first; list-related options drop the
@@ -542,6 +548,8 @@ int mgicp_debug_option(mgicp_ctx* ctx, const char* name, double value) {
   } else if (n == "vlist_stats") ctx->vl_stats = on;    // per-sweep list statistics on stderr
   else if (n == "fuse_compact") ctx->fuse_compact = on; // compaction fused into listed sweeps
   else if (n == "target_cache") ctx->tcache_on = on;    // adopt / leave the target state (process cache)
+  else if (n == "match_pairs_per_launch")               // mgicp_match_features: pairs of one launch (0: the default)
+    ctx->match_pairs_per_launch = value >= 1.0 ? static_cast<unsigned long long>(std::min(value, 9.0e18)) : kMatchPairsPerLaunch;
   else if (n == "bar_cmd") {                            // server commands through the BAR (else pinned copy)
     ctx->bar = on;
     if (!on && ctx->bar_cmd) {

@@ -1,6 +1,6 @@
 // mgicp_fod.hip -- the product calls beside the alignment (include/mi355x_gicp.h): point transforms,
-// cloud resolution, the radius filter, radius normals, boundary points, FPFH descriptors, segment
-// differences, Euclidean clustering and the voxel grid.
+// cloud resolution, the radius filter, radius normals, boundary points, FPFH descriptors, feature
+// correspondences, segment differences, Euclidean clustering and the voxel grid.
 #pragma clang fp contract(off)
 
 #include <hip/hip_runtime.h>
@@ -397,6 +397,112 @@ int mgicp_fpfh_features(mgicp_ctx* ctx, const float* xyz, size_t n, size_t strid
   inf.ms_device = t2 - t1;
   inf.ms_total = now_ms() - t0;
   if (info) *info = inf;
+  return MGICP_OK;
+}
+
+int mgicp_match_features(mgicp_ctx* ctx, const float* source, size_t n_source, size_t source_stride,
+                         const float* target, size_t n_target, size_t target_stride, double max_distance, int* match,
+                         float* distance, size_t* n_correspondences, mgicp_match_info* info) {
+  if (!ctx || !(max_distance >= 0) || (n_source && (!source || !match)) || (n_target && !target) ||
+      source_stride < 132 || (source_stride % 4) || target_stride < 132 || (target_stride % 4) ||
+      n_source > size_t(INT32_MAX) || n_target > size_t(INT32_MAX))
+    return MGICP_E_INVALID;
+  HIPCK(hipSetDevice(ctx->device));
+  const double t0 = now_ms();
+  mgicp_match_info inf{};
+  if (info) *info = inf;
+  if (n_correspondences) *n_correspondences = 0;
+  std::fill(ctx->match_stats, ctx->match_stats + 8, 0ll);
+  const float nanf_ = std::nanf("");
+  for (size_t i = 0; i < n_source; ++i) match[i] = -1;
+  if (distance) std::fill(distance, distance + n_source, nanf_);
+  // the rows with 33 finite values, packed, and the record each came from (ascending: the lowest packed
+  // row among equal distances is the lowest record)
+  auto pack = [](const float* base, size_t n, size_t stride, std::vector<float>& rows, std::vector<int>& rec) {
+    const unsigned char* p = reinterpret_cast<const unsigned char*>(base);
+    rows.reserve(n * 33);
+    rec.reserve(n);
+    for (size_t i = 0; i < n; ++i) {
+      float r[33];
+      std::memcpy(r, p + i * stride, sizeof(r));
+      bool ok = true;
+      for (int b = 0; b < 33; ++b) ok &= std::isfinite(r[b]);
+      if (!ok) continue;
+      rows.insert(rows.end(), r, r + 33);
+      rec.push_back(static_cast<int>(i));
+    }
+  };
+  std::vector<float> hs, ht;
+  std::vector<int> srec, trec;
+  pack(source, n_source, source_stride, hs, srec);
+  pack(target, n_target, target_stride, ht, trec);
+  const size_t ns = srec.size(), nt = trec.size();
+  inf.n_source_valid = static_cast<double>(ns);
+  inf.n_target_valid = static_cast<double>(nt);
+  if (ns == 0 || nt == 0) {  // nothing to search with, or nothing to search: every match stays -1
+    inf.ms_total = now_ms() - t0;
+    if (info) *info = inf;
+    return MGICP_OK;
+  }
+  // target rows of one launch, and the blocks that share them
+  const size_t chunk = static_cast<size_t>(
+      std::min<unsigned long long>(nt, std::max<unsigned long long>(1, ctx->match_pairs_per_launch / ns)));
+  const MatchLayout lay = match_layout(ns, chunk);
+  const uint32_t max_splits = std::max(lay.splits, (nt % chunk) ? match_layout(ns, nt % chunk).splits : 1u);
+  hipStream_t s = ctx->stream;
+  ScopedBuf<float> d_src, d_tgt;
+  ScopedBuf<unsigned long long> d_run, d_part, d_ctr;
+  std::vector<unsigned long long> keys(ns, kMatchNone);
+  HIPCK(d_src.reserve(ns * 33));
+  HIPCK(d_tgt.reserve(nt * 33));
+  HIPCK(d_run.reserve(ns));
+  if (max_splits > 1) HIPCK(d_part.reserve(static_cast<size_t>(max_splits) * ns));
+  HIPCK(d_ctr.reserve(3));
+  HIPCK(hipMemcpyAsync(d_src.p, hs.data(), ns * 33 * sizeof(float), hipMemcpyHostToDevice, s));
+  HIPCK(hipMemcpyAsync(d_tgt.p, ht.data(), nt * 33 * sizeof(float), hipMemcpyHostToDevice, s));
+  HIPCK(hipMemcpyAsync(d_run.p, keys.data(), ns * sizeof(unsigned long long), hipMemcpyHostToDevice, s));
+  HIPCK(hipMemsetAsync(d_ctr.p, 0, 3 * sizeof(unsigned long long), s));
+  int rc = sync(ctx);
+  if (rc) return rc;
+  const double t1 = now_ms();
+  long long launches = 0;
+  for (size_t b = 0; b < nt; b += chunk, ++launches)
+    HIPCK(launch_match(d_src.p, ns, d_tgt.p, b, std::min(nt, b + chunk), d_run.p, d_part.p, d_ctr.p, s));
+  if ((rc = sync(ctx))) return rc;
+  const double t2 = now_ms();
+  unsigned long long cut[3] = {0, 0, 0};
+  HIPCK(hipMemcpyAsync(keys.data(), d_run.p, ns * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+  HIPCK(hipMemcpyAsync(cut, d_ctr.p, sizeof(cut), hipMemcpyDeviceToHost, s));
+  if ((rc = sync(ctx))) return rc;
+  // PCL's rejection, in double: DBL_MAX squares to +inf and rejects nothing
+  const double max2 = max_distance * max_distance;
+  size_t n_corr = 0, n_tied = 0;
+  for (size_t k = 0; k < ns; ++k) {
+    const uint32_t low = static_cast<uint32_t>(keys[k]);
+    if (low == kMatchNoneLow) continue;
+    const uint32_t bits = static_cast<uint32_t>(keys[k] >> 32);
+    float d2;
+    std::memcpy(&d2, &bits, sizeof(d2));
+    if (static_cast<double>(d2) > max2) continue;
+    const size_t i = static_cast<size_t>(srec[k]);
+    match[i] = trec[low >> 1];
+    if (distance) distance[i] = d2;
+    ++n_corr;
+    n_tied += low & 1u;
+  }
+  if (n_correspondences) *n_correspondences = n_corr;
+  inf.n_correspondences = static_cast<double>(n_corr);
+  inf.n_tied = static_cast<double>(n_tied);
+  inf.pair_tests = static_cast<double>(ns) * static_cast<double>(nt);  // every pair is begun
+  inf.ms_device = t2 - t1;
+  inf.ms_total = now_ms() - t0;
+  if (info) *info = inf;
+  ctx->match_stats[0] = static_cast<long long>(ns) * static_cast<long long>(nt);
+  for (int v = 0; v < 3; ++v) ctx->match_stats[1 + v] = static_cast<long long>(cut[v]);
+  ctx->match_stats[4] = launches;
+  ctx->match_stats[5] = static_cast<long long>(chunk);
+  ctx->match_stats[6] = lay.splits;
+  ctx->match_stats[7] = lay.per_split;
   return MGICP_OK;
 }
 

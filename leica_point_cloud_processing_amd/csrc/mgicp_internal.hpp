@@ -374,6 +374,31 @@ hipError_t launch_fpfh_final(const GridView& g, const int* kp, size_t nk, const 
                              const uint16_t* rows, const int* msize, const unsigned int* too_big, float* out,
                              unsigned long long* ctr, hipStream_t s);
 
+// CorrespondenceEstimation over 33-float descriptors (InitialAlignment::obtainCorrespondences): exact brute
+// force.  src / tgt: ns / nt packed rows of 33 finite floats.  A source row's state is the key
+// (d2 bits << 32) | (target row << 1) | tied, kMatchNone before any target with d2 < FLT_MAX; keys order as
+// (d2, target row).  launch_match folds target rows [t_begin, t_end) into running[ns]: call it over
+// ascending ranges, at most pairs_per_launch / ns rows each, so that no launch is long.  partial:
+// match_layout(ns, rows of the largest range).splits * ns keys (unused when that is 1).
+// ctr (3 words, zeroed by the caller) += pairs left at the votes after bins 8, 16 and 24.
+constexpr uint32_t kMatchBlock = 256;            // threads = source rows of a block
+constexpr uint32_t kMatchSplitMin = 64;          // target rows of a block: a multiple of this
+constexpr uint32_t kMatchBlocksWanted = 8192;    // four rounds of 8 blocks per CU: the CUs' loads even out
+constexpr uint32_t kMatchNoneLow = 0xfffffffeu;  // row field 0x7fffffff (no row: n <= INT32_MAX), not tied
+constexpr unsigned long long kMatchNone = (0x7f7fffffull << 32) | kMatchNoneLow;  // d2 = FLT_MAX
+// pairs of one launch: 13 ms at the 6.0e11 pairs/s measured on the README's 198k x 198k shape, where the
+// votes leave 14 % of the pairs; about 20 ms at the 4.6e11 pairs/s of random rows, where they leave 7 %
+// (DESIGN.md "Feature correspondences")
+constexpr unsigned long long kMatchPairsPerLaunch = 1ull << 33;
+struct MatchLayout {
+  uint32_t splits;     // blocks that share the target rows of a launch (grid.y)
+  uint32_t per_split;  // target rows of each
+};
+MatchLayout match_layout(size_t ns, size_t count);
+hipError_t launch_match(const float* src, size_t ns, const float* tgt, size_t t_begin, size_t t_end,
+                        unsigned long long* running, unsigned long long* partial, unsigned long long* ctr,
+                        hipStream_t s);
+
 #if defined(MGICP_CORR_PHASES) && MGICP_CORR_PHASES
 hipError_t corr_phase_take(unsigned long long out[24]);  // diagnostic builds: read and reset
 #endif

@@ -4241,6 +4241,106 @@ __global__ __launch_bounds__(64) void fpfh_final_kernel(GridView g, const int* _
   if (lane == 0 && tests) atomicAdd(ctr + 2 * (blockIdx.x % kFpfhCtrSlots), tests);
 }
 
+// ------------------------------------------------------------------------------------
+// Feature correspondences (pcl::registration::CorrespondenceEstimation over FPFHSignature33, as
+// InitialAlignment::obtainCorrespondences calls it) -- DESIGN.md "Feature correspondences".
+// Exact brute force over packed rows of 33 floats, the non-finite rows already dropped by the host.
+//   match_kernel        a lane owns one source row in 33 VGPRs; the wave walks a range of target rows, whose
+//                       address is wave-uniform: their values come through scalar loads and reach the VALU
+//                       as SGPR operands.  d2 is the float sum in ascending bin order, product and sum each
+//                       rounded.  After bins 8, 16 and 24 the wave votes: the partial sums of non-negative
+//                       terms never fall, so a target whose partial sum is strictly above every lane's best
+//                       cannot win or tie in any lane and is left.  A lane's state is the key
+//                       (d2 bits << 32) | (target row << 1) | tied; d2 >= +0, so the keys order as (d2, row).
+//                       Block (x, y) starts from running[] -- the result over the targets of the launches
+//                       before -- and writes its own key to row y of partial[].
+//   match_merge_kernel  the least key of a source row's partials; tied when two of them hold one d2 at
+//                       different rows, or when one that holds the least d2 is tied itself.
+constexpr int kMatchBins = 33;
+constexpr int kMatchVote = 8;  // bins between two votes
+
+template <int B0, int B1>
+__device__ __forceinline__ float match_bins(const float (&s)[kMatchBins], const float* __restrict__ t, float d2) {
+#pragma unroll
+  for (int b = B0; b < B1; ++b) {
+    const float diff = s[b] - t[b];
+    d2 = d2 + diff * diff;
+    // the sum is one chain: keep the vectoriser from running it through packed adds with an idle half
+    asm("" : "+v"(d2));
+  }
+  return d2;
+}
+
+__global__ __launch_bounds__(256) void match_kernel(const float* __restrict__ src, uint32_t ns,
+                                                    const float* __restrict__ tgt, uint32_t t_begin, uint32_t t_end,
+                                                    uint32_t per_split, const unsigned long long* running,
+                                                    unsigned long long* partial, unsigned long long* __restrict__ ctr) {
+  const uint32_t i = blockIdx.x * kMatchBlock + threadIdx.x;
+  const bool live = i < ns;
+  const float* __restrict__ row = src + static_cast<size_t>(live ? i : 0u) * kMatchBins;
+  float s[kMatchBins];
+#pragma unroll
+  for (int b = 0; b < kMatchBins; ++b) s[b] = row[b];
+  const unsigned long long start = live ? running[i] : 0ull;
+  // a lane past the last row holds a best no partial sum is at or below: it never keeps the wave on a target
+  float best = live ? __uint_as_float(static_cast<uint32_t>(start >> 32)) : -1.f;
+  uint32_t low = static_cast<uint32_t>(start);
+  const unsigned long long first = static_cast<unsigned long long>(t_begin) + static_cast<unsigned long long>(blockIdx.y) * per_split;
+  const uint32_t j0 = static_cast<uint32_t>(first < t_end ? first : t_end);
+  const uint32_t j1 = (t_end - j0 > per_split) ? j0 + per_split : t_end;
+  uint32_t cut0 = 0, cut1 = 0, cut2 = 0;
+  for (uint32_t j = j0; j < j1; ++j) {
+    const float* __restrict__ t = tgt + static_cast<size_t>(j) * kMatchBins;
+    float d2 = match_bins<0, kMatchVote>(s, t, 0.f);
+    if (!__any(d2 <= best)) {
+      ++cut0;
+      continue;
+    }
+    d2 = match_bins<kMatchVote, 2 * kMatchVote>(s, t, d2);
+    if (!__any(d2 <= best)) {
+      ++cut1;
+      continue;
+    }
+    d2 = match_bins<2 * kMatchVote, 3 * kMatchVote>(s, t, d2);
+    if (!__any(d2 <= best)) {
+      ++cut2;
+      continue;
+    }
+    d2 = match_bins<3 * kMatchVote, kMatchBins>(s, t, d2);
+    if (d2 < best) {  // strict: FLANN's result set starts at FLT_MAX, and an earlier row keeps an equal d2
+      best = d2;
+      low = j << 1;
+    } else if (d2 == best && low != kMatchNoneLow) {
+      low |= 1u;
+    }
+  }
+  if (live) partial[static_cast<size_t>(blockIdx.y) * ns + i] = (static_cast<unsigned long long>(__float_as_uint(best)) << 32) | low;
+  // pairs left at each vote: the wave's targets times its live lanes
+  const unsigned long long lanes = static_cast<unsigned long long>(__popcll(__ballot(live)));
+  if ((threadIdx.x & 63) == 0 && lanes) {
+    if (cut0) atomicAdd(ctr + 0, cut0 * lanes);
+    if (cut1) atomicAdd(ctr + 1, cut1 * lanes);
+    if (cut2) atomicAdd(ctr + 2, cut2 * lanes);
+  }
+}
+
+__global__ void match_merge_kernel(const unsigned long long* __restrict__ partial, uint32_t ns, uint32_t splits,
+                                   unsigned long long* __restrict__ running) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= ns) return;
+  unsigned long long m = partial[i];
+  for (uint32_t k = 1; k < splits; ++k) {
+    const unsigned long long p = partial[static_cast<size_t>(k) * ns + i];
+    const bool same_d2 = (p >> 32) == (m >> 32);
+    const bool same_row = ((p ^ m) & 0xfffffffeull) == 0;
+    unsigned long long w = (p | 1ull) < (m | 1ull) ? p : m;  // by (d2, row): the tied bit does not order
+    // two partials that did not improve on running[] hold the same row: no tie by that
+    if (same_d2) w |= ((p | m) & 1ull) | (same_row ? 0ull : 1ull);
+    m = w;
+  }
+  running[i] = m;
+}
+
 __global__ __launch_bounds__(256) void reduce_finish_kernel(const double* __restrict__ partial,
                                                             int nb, double* __restrict__ out) {
   double acc[kRedVals];
@@ -5003,6 +5103,35 @@ hipError_t launch_fpfh_final(const GridView& g, const int* kp, size_t nk, const 
   return hipGetLastError();
 }
 
+MatchLayout match_layout(size_t ns, size_t count) {
+  const size_t bx = (ns + kMatchBlock - 1) / kMatchBlock;
+  // few source blocks: the targets of the launch are shared out until about kMatchBlocksWanted blocks run
+  size_t splits = std::max<size_t>(1, std::min<size_t>(kMatchBlocksWanted / std::max<size_t>(bx, 1),
+                                                       (count + kMatchSplitMin - 1) / kMatchSplitMin));
+  size_t per = (count + splits - 1) / splits;
+  per = std::max<size_t>(kMatchSplitMin, (per + kMatchSplitMin - 1) / kMatchSplitMin * kMatchSplitMin);
+  MatchLayout l;
+  l.per_split = static_cast<uint32_t>(per);
+  l.splits = static_cast<uint32_t>(std::max<size_t>(1, (count + per - 1) / per));
+  return l;
+}
+
+hipError_t launch_match(const float* src, size_t ns, const float* tgt, size_t t_begin, size_t t_end,
+                        unsigned long long* running, unsigned long long* partial, unsigned long long* ctr,
+                        hipStream_t s) {
+  if (!ns || t_end <= t_begin) return hipSuccess;
+  const MatchLayout l = match_layout(ns, t_end - t_begin);
+  const dim3 grid(nblk(ns, kMatchBlock), l.splits);
+  // one split: the block's key is the row's new running key
+  match_kernel<<<grid, kMatchBlock, 0, s>>>(src, static_cast<uint32_t>(ns), tgt, static_cast<uint32_t>(t_begin),
+                                            static_cast<uint32_t>(t_end), l.per_split, running,
+                                            l.splits > 1 ? partial : running, ctr);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess || l.splits == 1) return e;
+  match_merge_kernel<<<nblk(ns), 256, 0, s>>>(partial, static_cast<uint32_t>(ns), l.splits, running);
+  return hipGetLastError();
+}
+
 hipError_t launch_reduce_finish(const double* partial, int nb, double* out, hipStream_t s) {
   reduce_finish_kernel<<<1, kRedThreads, 0, s>>>(partial, nb, out);
   return hipGetLastError();
@@ -5415,6 +5544,8 @@ hipError_t preload_kernels(void* pinned, size_t pinned_bytes, hipStream_t s) {
       reinterpret_cast<const void*>(&fpfh_list_kernel),
       reinterpret_cast<const void*>(&fpfh_spfh_kernel),
       reinterpret_cast<const void*>(&fpfh_final_kernel),
+      reinterpret_cast<const void*>(&match_kernel),
+      reinterpret_cast<const void*>(&match_merge_kernel),
   };
   for (const void* f : fns) {
     hipFuncAttributes attr;

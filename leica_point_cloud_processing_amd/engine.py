@@ -312,6 +312,36 @@ class GICPEngine:
         info = {f: getattr(fi, f) for f, _ in fi._fields_}
         return (fpfh[:nk], counts[:n] if want_spfh else None, sizes[:n] if want_spfh else None, info)
 
+    @staticmethod
+    def _feature_arg(features, what: str):
+        """(keepalive array, n, stride in bytes) of float32 rows of at least 33 values"""
+        f = np.asarray(features)
+        if f.ndim != 2 or f.shape[1] < 33:
+            raise ValueError(f"{what} must be [n, 33] (or wider rows), got {f.shape}")
+        f = np.ascontiguousarray(f, dtype=np.float32)
+        return f, len(f), 4 * f.shape[1]
+
+    def match_features(self, source_features, target_features, max_distance: float | None = None):
+        """pcl::registration::CorrespondenceEstimation::determineCorrespondences over FPFHSignature33
+        (InitialAlignment::obtainCorrespondences): (match int32[ns], distance float32[ns], info).  The inputs are
+        float32 [n, 33], or wider rows whose first 33 values are the descriptor (passed with their stride).
+        match[i] is the target row with the smallest float squared distance to source row i (equal distances:
+        the lowest row), distance[i] that squared distance; -1 and NaN for a source row with a non-finite
+        value, without a finite target row, or farther than max_distance (None: DBL_MAX, nothing rejected)."""
+        src, ns, sstride = self._feature_arg(source_features, "source_features")
+        tgt, nt, tstride = self._feature_arg(target_features, "target_features")
+        match = np.full(max(ns, 1), -1, np.int32)
+        dist = np.full(max(ns, 1), np.nan, np.float32)
+        cnt = ctypes.c_size_t()
+        mi = _lib.MgicpMatchInfo()
+        self._check(self._lib.mgicp_match_features(
+            self._h, ctypes.c_void_p(src.ctypes.data) if ns else None, ns, sstride,
+            ctypes.c_void_p(tgt.ctypes.data) if nt else None, nt, tstride,
+            float(np.finfo(np.float64).max) if max_distance is None else float(max_distance),
+            match.ctypes.data, dist.ctypes.data, ctypes.byref(cnt), ctypes.byref(mi)), "match_features")
+        info = {f: getattr(mi, f) for f, _ in mi._fields_}
+        return match[:ns], dist[:ns], info
+
     # -- FOD-side callers (SURVEY.md 8f rows 2 and 4) ------------------------------------------
     def segment_differences(self, cloud_in, cloud_sub, sqr_threshold: float, T=None):
         """pcl::SegmentDifferences (Filter::removeFromCloud): bool keep mask over cloud_in (after T)
@@ -418,6 +448,15 @@ class GICPEngine:
         cnt = self._check(self._lib.mgicp_debug_target_cov_slice(self._h, int(nranks), int(rank), _dp(out)),
                           "debug_target_cov_slice")
         return out[:cnt].copy()
+
+    MATCH_STATS = ("pairs", "left_after_8", "left_after_16", "left_after_24", "launches", "rows_per_launch",
+                   "splits", "rows_per_split")
+
+    def match_stats(self) -> dict:
+        """The last match_features call of this engine (mgicp_debug_match_stats)."""
+        out = (ctypes.c_longlong * 8)()
+        self._check(self._lib.mgicp_debug_match_stats(self._h, out), "match_stats")
+        return {k: int(out[i]) for i, k in enumerate(self.MATCH_STATS)}
 
     VLIST_STATS = ("requested", "pending", "lists", "entries", "reject", "overflow", "pool_used", "cells")
 

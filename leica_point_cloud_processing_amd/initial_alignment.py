@@ -1,9 +1,10 @@
 """InitialAlignment -- the pre-alignment's steps that run on the MI355X engine.
 
-Two members of the reference class (src/InitialAlignment.cpp): obtainBoundaryKeypoints, the keypoint step
-of the BOUNDARY (default) and NORMALS methods, and obtainFeatures, the FPFH descriptors at the keypoints
-(BOUNDARY and HARRIS).  The normals they take come from gicp_alignment.getNormals (Utils::getNormals); the
-feature correspondences and the RANSAC rejector are not on the engine yet.
+Three members of the reference class (src/InitialAlignment.cpp): obtainBoundaryKeypoints, the keypoint step
+of the BOUNDARY (default) and NORMALS methods, obtainFeatures, the FPFH descriptors at the keypoints
+(BOUNDARY and HARRIS), and obtainCorrespondences, the nearest target descriptor of every source descriptor.
+The normals they take come from gicp_alignment.getNormals (Utils::getNormals).  Only the rejectors
+(rejectCorrespondences, rejectOneToOneCorrespondences) and estimateTransform remain off the engine.
 """
 from __future__ import annotations
 
@@ -60,3 +61,18 @@ def obtainFeatures(cloud, normals, keypoints_indices, radius_factor: float = RAD
     radius = engine.cloud_resolution(cloud) * radius_factor
     features, _counts, _sizes, _info = engine.fpfh_features(cloud, normals, keypoints, radius)
     return (-1 if len(features) == 0 else 0), features
+
+
+def obtainCorrespondences(source_features, target_features, engine: GICPEngine | None = None):
+    """InitialAlignment::obtainCorrespondences (src/InitialAlignment.cpp:510-517):
+    pcl::registration::CorrespondenceEstimation::determineCorrespondences with its default max_distance
+    (nothing rejected).  The features are float32 [n, 33] (obtainFeatures' arrays).  Returns (index_query
+    int32[m], index_match int32[m], distance float32[m]) -- the fields of pcl::Correspondences, one entry per
+    source feature that found a target, in ascending index_query; distance is the squared L2 distance."""
+    if engine is None:
+        from .filter import _engine
+
+        engine = _engine()
+    match, distance, _info = engine.match_features(source_features, target_features)
+    index_query = np.flatnonzero(match >= 0).astype(np.int32)
+    return index_query, match[index_query], distance[index_query]

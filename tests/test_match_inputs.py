@@ -1,0 +1,222 @@
+"""CPU tests of the correspondence cases (tests/match_cases.py): every case is what it claims to be, and the
+float32 reference agrees with an independent fp64 brute force wherever the fp64 gap between the best and the
+runner-up exceeds the float rounding bound -- so the reference is the specified nearest neighbour, not an
+artefact of its own arithmetic.  Also: the ctypes mirror matches the header, the adapter compiles against its
+stand-ins, and the Python mirror is there."""
+import ctypes
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import match_cases as mc
+from conftest import ROOT
+
+
+@pytest.mark.parametrize("name", mc.CASES)
+def test_shapes_and_reference_invariants(name):
+    S, T, md = mc.case(name)
+    ref = mc.case_reference(name)
+    ns, nt = len(S), len(T)
+    assert S.dtype == np.float32 and T.dtype == np.float32 and S.shape == (ns, 33) and T.shape == (nt, 33)
+    assert ref.match.dtype == np.int32 and ref.match.shape == (ns,)
+    assert ref.distance.dtype == np.float32 and ref.distance.shape == (ns,)
+    np.testing.assert_array_equal(ref.source_valid, np.isfinite(S).all(1) if ns else np.zeros(0, bool))
+    np.testing.assert_array_equal(ref.target_valid, np.isfinite(T).all(1) if nt else np.zeros(0, bool))
+    got = ref.match >= 0
+    # NaN exactly where there is no match; a match is a valid target of a valid query, below FLT_MAX
+    np.testing.assert_array_equal(np.isnan(ref.distance), ~got)
+    assert ref.source_valid[got].all() and ref.target_valid[ref.match[got]].all()
+    assert (ref.distance[got] < mc.FLT_MAX).all() and (ref.distance[got] >= 0).all()
+    assert ref.n_correspondences == got.sum() and ref.n_tied == ref.tied.sum() and not ref.tied[~got].any()
+    if md is None and ref.n_target_valid:
+        # nothing rejected: only an invalid query or one with every d2 at or above FLT_MAX goes without
+        assert (got | ~ref.source_valid | ~(ref.best < mc.FLT_MAX)).all()
+    if ref.n_target_valid == 0:
+        assert not got.any()
+    # the distance is the d2 of the pair the match names, recomputed on its own
+    for i in np.flatnonzero(got)[:: max(1, int(got.sum()) // 50)]:
+        assert mc.d2_matrix(S[i:i + 1], T[ref.match[i]:ref.match[i] + 1])[0, 0] == ref.distance[i]
+
+
+def test_cases_are_what_they_claim():
+    kp, res3 = mc.fpfh_rows("part_kp"), mc.fpfh_rows("part_3res")
+    assert kp.shape == (2069, 33) and res3.shape == (2069, 33)
+    zero = ~kp.any(1)
+    assert zero.sum() == 464 and len(np.unique(kp, axis=0)) == 1020
+    # kp_vs_kp: hundreds of queries decided by the index rule (the 464 zero rows alone tie 464 ways)
+    ref = mc.case_reference("kp_vs_kp")
+    print("kp_vs_kp tied", ref.n_tied, "of", ref.n_correspondences)
+    assert ref.n_tied >= 464 and ref.tied[zero].all() and ref.n_correspondences == 2069
+    assert (ref.match[zero] == np.flatnonzero(zero)[0]).all() and (ref.distance[zero] == 0).all()
+    assert (ref.distance == 0).all() and (ref.match <= np.arange(2069)).all()
+    # kp_vs_3res: none; 3res_vs_kp: exactly two
+    assert mc.case_reference("kp_vs_3res").n_tied == 0 and mc.case_reference("kp_vs_3res").n_correspondences == 2069
+    assert mc.case_reference("3res_vs_kp").n_tied == 2
+    # nonfinite: 655 rows, 43 of them NaN, 10 zero; with 5 % of the targets NaN in bin 0, 16 or 32 alone
+    S, T, _ = mc.case("nonfinite")
+    bad = ~np.isfinite(S).all(1)
+    assert S.shape == (655, 33) and bad.sum() == 43 and (~S[~bad].any(1)).sum() == 10
+    ref = mc.case_reference("nonfinite")
+    assert (ref.match[bad] == -1).all() and (ref.match[~bad] >= 0).all() and ref.n_source_valid == 612
+    S2, T2, _ = mc.case("nonfinite_target_nan")
+    nan = np.isnan(T2)
+    rows = nan.any(1)
+    assert rows.sum() == round(0.05 * 2069) and (nan.sum(1)[rows] == 1).all()
+    assert all(nan[rows, b].sum() >= 30 for b in (0, 16, 32)) and nan[:, [0, 16, 32]].sum() == rows.sum()
+    assert (T2[~nan] == T[~nan]).all()
+    ref2 = mc.case_reference("nonfinite_target_nan")
+    assert not rows[ref2.match[ref2.match >= 0]].any() and ref2.n_target_valid == 2069 - rows.sum()
+    changed = (ref2.match != ref.match).sum()
+    print("nonfinite: queries whose winner was dropped with the NaN targets", int(changed))
+    assert changed >= 5
+    # the edge cases
+    assert mc.case_reference("all_target_nan").n_target_valid == 0 and len(mc.case("all_target_nan")[1]) == 50
+    assert np.isnan(mc.case("all_target_nan")[1]).sum(1).tolist() == [1] * 50
+    assert len(mc.case("nt0")[1]) == 0 and len(mc.case("ns0")[0]) == 0 and len(mc.case("ns0")[1]) == 100
+    assert mc.case_reference("ns1_nt1").match.tolist() == [0]
+    assert (mc.case_reference("nt1").match == 0).all() and len(mc.case("nt1")[0]) == 100
+    # sizes: feature blocks that sum to 100; the shapes asked for
+    assert len(mc.SIZES_CASES) == 35
+    for name in mc.SIZES_CASES + ("multi_block",):
+        S, T, _ = mc.case(name)
+        ns, nt = (4099, 10007) if name == "multi_block" else (int(v) for v in name.split("_")[1:])
+        assert S.shape == (ns, 33) and T.shape == (nt, 33) and (S >= 0).all() and (T >= 0).all()
+        for X in (S, T):
+            assert np.abs(X.reshape(-1, 3, 11).astype(np.float64).sum(2) - 100).max() < 1e-3
+        assert mc.case_reference(name).n_correspondences == ns
+    # late_bins: bins 0 .. 31 are one row; the winner is the last target, by bin 32 alone
+    S, T, _ = mc.case("late_bins")
+    assert (S[:, :32] == S[0, :32]).all() and (T[:, :32] == S[0, :32]).all()
+    ref = mc.case_reference("late_bins")
+    assert (ref.match == mc.LATE_NT - 1).all() and ref.n_tied == 0 and len(S) == mc.LATE_NS
+    assert (T[:-1, 32] > T[-1, 32]).all() and (S[:, 32] < T[-1, 32]).all()
+    # dups: every target row three times; every matched query tied, the winner the lowest of the copies
+    S, T, _ = mc.case("dups")
+    _u, inv, cnt = np.unique(T, axis=0, return_inverse=True, return_counts=True)
+    assert (cnt % 3 == 0).all() and len(T) == 1200
+    ref = mc.case_reference("dups")
+    assert ref.n_tied == ref.n_correspondences == len(S)
+    first = np.full(len(cnt), len(T))
+    np.minimum.at(first, inv.ravel(), np.arange(len(T)))
+    np.testing.assert_array_equal(ref.match, first[inv.ravel()[ref.match]])
+    # huge: the overflow pattern
+    S, T, _ = mc.case("huge")
+    D = mc.d2_matrix(S, T)
+    sq = np.float32(1e19) * np.float32(1e19)
+    assert np.isinf(D[:, 1:3]).all() and np.isinf(D[2]).all() and np.isinf(D[5]).all()
+    assert D[0, 0] == sq and D[1, 0] == sq + sq and D[1, 3] == sq and D[1, 4] == sq and sq < mc.FLT_MAX
+    ref = mc.case_reference("huge")
+    assert tuple(ref.match.tolist()) == mc.HUGE_EXPECT and tuple(ref.tied.tolist()) == mc.HUGE_TIED
+    # winner_case: the winner is where it was put, and unique
+    for pos in (0, 63, 64, 999):
+        q, T = mc.winner_case(1000, pos)
+        r = mc.reference(q, T)
+        assert r.match.tolist() == [pos] and r.n_tied == 0 and r.distance[0] == np.float32(0.0625)
+
+
+def test_max_distance_cases():
+    base = mc.case_reference("kp_vs_3res")
+    q = mc.maxdist_query()
+    d2 = np.float64(base.distance[q])
+    assert d2 > 0
+    mds = {name: mc.case(name)[2] for name in mc.MAXDIST_CASES}
+    assert mds["maxdist_zero"] == 0.0 and mds["maxdist_dblmax"] == mc.DBL_MAX
+    assert mds["maxdist_below"] < mds["maxdist_at"] < mds["maxdist_above"]
+    assert mds["maxdist_at"] == np.sqrt(d2) and mds["maxdist_above"] == np.nextafter(mds["maxdist_at"], np.inf)
+    for name, md in mds.items():
+        ref = mc.case_reference(name)
+        with np.errstate(over="ignore"):
+            keep = ~(base.distance.astype(np.float64) > np.float64(md) * np.float64(md))
+        np.testing.assert_array_equal(ref.match, np.where(keep, base.match, -1))
+        print(name, md, "kept", int(keep.sum()), "query", q, "kept", bool(keep[q]))
+    # 0 keeps exactly the queries at distance 0; DBL_MAX everything; the three around the query differ at it
+    assert (mc.case_reference("maxdist_zero").match >= 0).sum() == (base.distance == 0).sum()
+    np.testing.assert_array_equal(mc.case_reference("maxdist_dblmax").match, base.match)
+    assert mc.case_reference("maxdist_below").match[q] == -1 and mc.case_reference("maxdist_above").match[q] == base.match[q]
+    assert 0 < mc.case_reference("maxdist_at").n_correspondences < 2069
+
+
+@pytest.mark.parametrize("name", ("kp_vs_3res", "3res_vs_kp", "nonfinite_target_nan", "sizes_257_4099", "dups"))
+def test_reference_agrees_with_fp64_brute_force(name):
+    """d2 in float: 33 differences, 33 products and 32 sums, each within 2^-24 relative, all terms non-negative:
+    |float d2 - exact d2| <= 35 * 2^-24 * exact d2 (first order, 36 with the margin).  Where the fp64 runner-up
+    exceeds the fp64 best by more than twice that bound of the runner-up, the float argmin must be fp64's."""
+    S, T, _ = mc.case(name)
+    ref = mc.case_reference(name)
+    sv, tv = ref.source_valid, ref.target_valid
+    tidx = np.flatnonzero(tv)
+    best, arg, second = mc.d2_f64(S[sv], T[tv])
+    bound = 36.0 * 2.0 ** -24
+    clear = second - best > 2.0 * bound * second
+    got = ref.match[sv]
+    print(name, "queries", int(sv.sum()), "clear in fp64", int(clear.sum()))
+    assert clear.sum() >= (0 if name == "dups" else sv.sum() // 2)
+    np.testing.assert_array_equal(got[clear], tidx[arg][clear])
+    assert not ref.tied[sv][clear].any()
+    # and the distance itself is within the bound of the fp64 one
+    assert (np.abs(ref.distance[sv].astype(np.float64) - best) <= bound * best).all()
+    if name == "dups":  # every minimum is attained three times in fp64 too
+        assert (second == best).all()
+
+
+def test_python_binding_matches_header():
+    """mgicp_match_info: the ctypes mirror has the header's fields in the header's order, all double; the
+    prototype has the header's twelve arguments."""
+    from leica_point_cloud_processing_amd import _lib
+
+    text = open(_lib.HEADER_PATH).read()
+    body = re.search(r"typedef struct \{([^}]*)\}\s*mgicp_match_info;", text).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    fields = []
+    for typ, names in re.findall(r"\b(double|int)\s+([\w\s,]+);", body):
+        fields += [(n.strip(), typ) for n in names.split(",")]
+    assert [(n, {"double": ctypes.c_double, "int": ctypes.c_int}[t]) for n, t in fields] == list(_lib.MgicpMatchInfo._fields_)
+    assert [n for n, _ in fields] == ["n_source_valid", "n_target_valid", "n_correspondences", "n_tied", "pair_tests",
+                                      "ms_device", "ms_total"]
+    assert ctypes.sizeof(_lib.MgicpMatchInfo) == 56
+    proto = re.sub(r"/\*.*?\*/", "", re.search(r"int mgicp_match_features\((.*?)\);", text, flags=re.S).group(1), flags=re.S)
+    args = [a.strip() for a in proto.split(",")]
+    res, argtypes = _lib._SIGNATURES["mgicp_match_features"]
+    assert res is ctypes.c_int and len(args) == len(argtypes) == 12
+    want = {"mgicp_ctx*": ctypes.c_void_p, "const float*": ctypes.c_void_p, "size_t": ctypes.c_size_t,
+            "double": ctypes.c_double, "int*": ctypes.c_void_p, "float*": ctypes.c_void_p,
+            "size_t*": ctypes.POINTER(ctypes.c_size_t), "mgicp_match_info*": ctypes.POINTER(_lib.MgicpMatchInfo)}
+    for a, t in zip(args, argtypes):
+        assert want[a.rsplit(" ", 1)[0]] == t, a
+    assert "mgicp_match_features" in _lib.header_symbols(_lib.HEADER_PATH)
+    assert "mgicp_debug_match_stats" in _lib.header_symbols(_lib.DEBUG_HEADER_PATH)
+
+
+def test_correspondences_adapter_compiles_against_standins():
+    """adapter/InitialAlignment_correspondences_mi355x.cpp compiles as the catkin package would compile it,
+    against the stand-in headers of tests/adapter_standins_corr, and links to libmgicp.so through product
+    symbols only."""
+    from leica_point_cloud_processing_amd import _lib
+
+    r = subprocess.run(["make", "-s", "-C", ROOT, "corr-replay"], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    exe = os.path.join(ROOT, "adapter", "build", "replay_test_correspondences")
+    assert os.path.exists(exe)
+    nm = subprocess.run(["nm", "-C", exe], capture_output=True, text=True).stdout
+    assert "InitialAlignment::obtainCorrespondences" in nm
+    needed = {line.split()[-1] for line in subprocess.run(["nm", "-u", exe], capture_output=True, text=True).stdout.splitlines()
+              if line.split() and line.split()[-1].startswith("mgicp_")}
+    assert "mgicp_match_features" in needed
+    assert needed <= set(_lib.header_symbols(_lib.HEADER_PATH)), sorted(needed)
+
+
+def test_obtainCorrespondences_is_importable_and_checks_shapes():
+    from leica_point_cloud_processing_amd import initial_alignment
+    from leica_point_cloud_processing_amd.engine import GICPEngine
+
+    assert callable(initial_alignment.obtainCorrespondences) and callable(GICPEngine.match_features)
+    assert "obtainCorrespondences" in initial_alignment.__doc__
+    # a wrong shape is refused before any device work
+    for bad in (np.zeros((4, 32), np.float32), np.zeros(33, np.float32), np.zeros((2, 3, 33), np.float32)):
+        with pytest.raises(ValueError):
+            GICPEngine._feature_arg(bad, "source_features")
+    f, n, stride = GICPEngine._feature_arg(np.zeros((4, 40)), "source_features")
+    assert f.dtype == np.float32 and n == 4 and stride == 160
