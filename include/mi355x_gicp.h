@@ -66,7 +66,8 @@ typedef struct {
     int    converged;       /* Registration::hasConverged() */
     int    iterations;      /* GICP nr_iterations_ */
     int    n_corr;          /* correspondences in the last outer iteration (all ranks) */
-    int    n_evals;         /* BFGS objective passes over the correspondences */
+    int    n_evals;         /* BFGS objective passes run over the correspondences (evaluations whose fp32
+                               transform the run had already passed over take no pass and do not count) */
     double ms_total;        /* host call -> transform on host */
     double ms_upload;       /* host -> HBM copies of dirty clouds */
     double ms_prep;         /* grid build + kNN covariances (one-time per set_*) */

@@ -87,8 +87,10 @@ int mgicp_debug_kernel_times(mgicp_ctx* ctx, double out_ms[MGICP_KERNEL_FAMILIES
  * from device memory the host writes through the BAR, [5] private host-row buffer allocations,
  * [6] transport (0 local, 1 RCCL, 2 shared segment, 3 shared segment + RCCL, 4 xGMI row exchange
  * over the segment, 5 xGMI row exchange + RCCL), [7] server launches
- * refused because another context of this process ran a server on the same device */
-int mgicp_debug_pass_stats(mgicp_ctx* ctx, long long out[8]);
+ * refused because another context of this process ran a server on the same device, [8] objective
+ * evaluations answered without a pass: their fp32 transform had been passed over in the same BFGS
+ * run (debug option "pass_memo"), so [1] + [2] - [3] + [8] is what n_evals would be without */
+int mgicp_debug_pass_stats(mgicp_ctx* ctx, long long out[9]);
 /* the resident pass server as the aligns run it (always on, two HIP events per server launch on the
  * engine's stream, resolved when an align drains): *out_ms = summed device duration of the server
  * launches (first command .. cancel, host round trips between passes included), *out_passes = the

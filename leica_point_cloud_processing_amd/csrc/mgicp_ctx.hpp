@@ -19,6 +19,7 @@
 
 #include "../../include/mi355x_gicp.h"
 #include "mgicp_internal.hpp"
+#include "pass_memo.hpp"
 #include "pcl_bfgs.hpp"
 #include "shm_rows.hpp"
 
@@ -162,8 +163,10 @@ enum {
   kStTransport,      // 0 local, 1 RCCL, 2 shared segment, 3 shared segment + RCCL (bulk all-gathers),
                      // 4 xGMI row exchange (+ segment), 5 xGMI row exchange + RCCL
   kStSrvDenied,      // server launches refused because another context of this process held the device
+  kStMemoHit,        // objective evaluations answered from the run's table of evaluated transforms: no pass ran
   kStCount
 };
+static_assert(kStCount == 9, "mgicp_debug_pass_stats writes out[9]: engine.py's buffer and PASS_STATS follow");
 
 // r05 target cache: one entry per device (its DevBufs belong to no context: grave = nullptr)
 struct TargetCache {
@@ -405,6 +408,9 @@ struct mgicp_ctx {
   Mat4 last_guess = Mat4::identity();
   std::vector<float> trace;
   int n_evals = 0;
+  // debug option "pass_memo" (0: every evaluation at a new x is a device pass): an evaluation whose fp32
+  // transform the BFGS run has already passed over takes that pass's sums (pass_memo.hpp)
+  bool pass_memo = true;
   // profiling
   bool profiling = false;
   unsigned long long prof_tick = 0;
@@ -531,7 +537,11 @@ int ensure_rows(mgicp_ctx* ctx);
 int wait_rows(mgicp_ctx* ctx, unsigned int rstamp, const Xf34& A, double out[kRedVals], bool allow_takeover);
 int ensure_iter_buffers(mgicp_ctx* ctx);
 int combine_to_host(mgicp_ctx* ctx, int nv, const double* sup, double* out);
-// OptimizationFunctorWithIndices::fdf on the device; memoises the last state
+// OptimizationFunctorWithIndices::fdf on the device; memoises the last state, and the sums of every
+// pass of its BFGS run by the fp32 transform the pass was given.  One functor per run (estimate_bfgs
+// constructs it): the table must not outlive the run's correspondences.  Every rank runs the same host
+// BFGS on bit-identical totals, so every rank hits and misses on the same evaluations; nothing
+// per-rank (timing, a take-over) feeds the decision, and row stamps advance only in pass().
 struct DeviceFunctor {
   mgicp_ctx* ctx;
   bool have_memo = false;
@@ -539,11 +549,15 @@ struct DeviceFunctor {
   double memo_f = 0;
   Vec6 memo_g{};
   double m = 0;  // correspondences of this sweep (all ranks)
+  PassMemo seen{};  // (transform, sums) of this run's passes (ctx->pass_memo)
 
-  int pass(const Vec6& x, double sums[kRedVals]);         // one objective pass at x: its 16 raw sums
+  int pass(const Vec6& x, double sums[kRedVals]);         // one objective pass at x: its 16 raw sums (never memoised)
+  void remember(const Vec6& x, const double s[kRedVals]);  // the sums of the pass at x into the run's table
   void memoise(const Vec6& x, const double s[kRedVals]);  // f and g at x from the sums of the pass at x
   int eval(const Vec6& x, double& f, Vec6& g);
 };
+static_assert(PassMemo::kVals == kRedVals && sizeof(Xf34) == PassMemo::kKeyFloats * sizeof(float),
+              "pass_memo.hpp restates the pass's key and value sizes");
 struct GateGuard {  // a BFGS run leaves no gated pass queued behind it
   mgicp_ctx* ctx;
   ~GateGuard() { cancel_gated(ctx); }

@@ -18,7 +18,7 @@
 
 extern "C" {
 
-int mgicp_debug_pass_stats(mgicp_ctx* ctx, long long out[8]) {
+int mgicp_debug_pass_stats(mgicp_ctx* ctx, long long out[9]) {
   if (!ctx || !out) return MGICP_E_INVALID;
   for (int i = 0; i < kStCount; ++i) out[i] = ctx->st[i];
   return MGICP_OK;
@@ -528,6 +528,7 @@ int mgicp_debug_option(mgicp_ctx* ctx, const char* name, double value) {
   else if (n == "srv_cus") ctx->srv_cus = std::max(0, iv);  // cap on the server's blocks (0 = every CU)
   else if (n == "fused_finish") ctx->fused_finish = on; // in-launch reduction finish of launched passes
   else if (n == "gated") ctx->gated = on;               // launched passes pre-queued behind a command gate
+  else if (n == "pass_memo") ctx->pass_memo = on;       // no pass at a transform the BFGS run has passed over (else one per new x)
   else if (n == "async_cov") ctx->async_tgt = on && ctx->aux_stream;  // set_*'s covariance head start
   else if (n == "lazy_src_cov") {                       // source covariances of accepted points only
     ctx->lazy_src_cov = on;

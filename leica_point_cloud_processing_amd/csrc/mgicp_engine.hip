@@ -274,6 +274,7 @@ int estimate_bfgs(mgicp_ctx* ctx, Mat4& T, int* n_corr) {
   *n_corr = static_cast<int>(s[13]);
   if (s[13] < 4) return MGICP_E_SOLVER;  // NotEnoughPointsException
   fn.memoise(x, s);  // seed the memo with this pass so minimizeInit reuses it
+  fn.remember(x, s);  // and the run's table: the line search comes back to this transform
   PclBfgs<DeviceFunctor> bfgs(fn);
   const double gradient_tol = 1e-2;
   int inner = 0;

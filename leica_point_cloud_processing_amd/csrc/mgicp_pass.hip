@@ -773,13 +773,27 @@ void DeviceFunctor::memoise(const Vec6& x, const double s[kRedVals]) {
   have_memo = true;
 }
 
+void DeviceFunctor::remember(const Vec6& x, const double s[kRedVals]) {
+  if (ctx->pass_memo) seen.insert(apply_state(x).xf().m, s);
+}
+
 int DeviceFunctor::eval(const Vec6& x, double& f, Vec6& g) {
   if (!(have_memo && std::memcmp(x.v, memo_x.v, sizeof(x.v)) == 0)) {
-    double s[kRedVals];
-    int rc = pass(x, s);
-    if (rc) return rc;
-    memoise(x, s);
-    ptimes_eval(ctx);
+    // a new x whose fp32 transform this run has passed over already: the pass would return the sums
+    // held (bitwise), so only f and g are taken again, g with the new x (pass_memo.hpp)
+    const Xf34 A = apply_state(x).xf();
+    const double* held = ctx->pass_memo ? seen.find(A.m) : nullptr;
+    if (held) {
+      ctx->st[kStMemoHit]++;
+      memoise(x, held);
+    } else {
+      double s[kRedVals];
+      int rc = pass(x, s);
+      if (rc) return rc;
+      if (ctx->pass_memo) seen.insert(A.m, s);
+      memoise(x, s);
+      ptimes_eval(ctx);
+    }
   }
   f = memo_f;
   g = memo_g;

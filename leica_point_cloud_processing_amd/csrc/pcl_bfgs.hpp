@@ -3,9 +3,11 @@
 // Restates pcl/registration/bfgs.h (a port of GSL's vector_bfgs2 with Fletcher's line
 // search) and GICP::estimateRigidTransformationBFGS (registration/impl/gicp.hpp) so that
 // the engine follows the same iterate sequence as the reference's PCL CPU GICP
-// (SURVEY.md 8a a6, Appendix A.5).  Every objective evaluation is a device pass; the
+// (SURVEY.md 8a a6, Appendix A.5).  An objective evaluation is a device pass; the
 // functor always returns f AND the gradient, and memoises the last state so the
-// f / df / fdf cache protocol of bfgs.h costs no extra passes and yields identical values.
+// f / df / fdf cache protocol of bfgs.h costs no extra passes and yields identical values
+// (and, pass_memo.hpp, the sums of every pass of the run by its fp32 transform: the line
+// search's closing evaluations at transforms already passed over cost none either).
 //
 // Two details of PCL 1.8.1's interpolate() are kept exactly as published:
 //   the cubic branch is guarded by !(fpb != fpa) (GSL: fpb is real), and the quadratic

@@ -421,11 +421,11 @@ class GICPEngine:
         self._check(self._lib.mgicp_comm_attach_shm(self._h, None, 0), "comm_attach_shm(detach)")
 
     PASS_STATS = ("server_launches", "server_passes", "launched_passes", "takeovers", "bar_commands",
-                  "row_allocs", "transport", "server_denied")
+                  "row_allocs", "transport", "server_denied", "memo_hits")
 
     def pass_stats(self) -> dict:
         """Objective-pass path counters (mgicp_debug_pass_stats)."""
-        out = (ctypes.c_longlong * 8)()
+        out = (ctypes.c_longlong * len(self.PASS_STATS))()
         self._check(self._lib.mgicp_debug_pass_stats(self._h, out), "pass_stats")
         return {k: int(out[i]) for i, k in enumerate(self.PASS_STATS)}
 
