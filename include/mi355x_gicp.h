@@ -53,7 +53,8 @@ typedef struct {
     double tf_eps;          /* setTransformationEpsilon             (GICPAlignment.cpp:52; default 4e-3) */
     double rot_eps;         /* GICP rotation_epsilon_                (PCL default 2e-3) */
     double max_corr_dist;   /* setMaxCorrespondenceDistance          (GICPAlignment.cpp:51; default 0.04) */
-    double gicp_eps;        /* GICP gicp_epsilon_                    (PCL default 1e-3) */
+    double gicp_eps;        /* GICP gicp_epsilon_                    (PCL default 1e-3; finite and >= 0, 0 legal as
+                               in PCL: a NaN, negative or infinite value is refused with MGICP_E_INVALID) */
     int    k;               /* GICP k_correspondences_               (PCL default 20; any k in [1, 32]) */
     int    max_inner_iter;  /* GICP max_inner_iterations_            (PCL default 20) */
     int    solver;          /* MGICP_SOLVER_* */

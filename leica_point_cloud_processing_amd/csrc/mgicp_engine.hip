@@ -343,6 +343,9 @@ int estimate_gn(mgicp_ctx* ctx, Mat4& T, int* n_corr) {
 int check_params(mgicp_ctx* ctx, const mgicp_params& p) {
   if (p.k < 1 || p.k > kMaxK)
     return fail(ctx, MGICP_E_INVALID, "k (k_correspondences) must be in [1, 32]");
+  // 0 is PCL's legal degenerate value; a NaN, negative or infinite one makes every covariance NaN or indefinite
+  if (!(p.gicp_eps >= 0) || std::isinf(p.gicp_eps))
+    return fail(ctx, MGICP_E_INVALID, "gicp_eps (gicp_epsilon) must be finite and >= 0");
   if (p.max_iter < 1 || p.max_inner_iter < 1 || !(p.max_corr_dist >= 0) || !(p.rot_eps > 0) ||
       !(p.tf_eps >= 0) ||
       (p.solver != MGICP_SOLVER_PCL_BFGS && p.solver != MGICP_SOLVER_GN))

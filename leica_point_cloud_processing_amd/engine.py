@@ -60,6 +60,7 @@ class GICPEngine:
         if rc != 0:
             raise _lib.MgicpError(rc, "mgicp_create failed (no HIP device or invalid parameters)")
         self._h = h
+        self._pushed = type(self.params).from_buffer_copy(self.params)  # what the context holds
         _LIVE.add(id(self))
         self.ransac_outlier_threshold = 0.05
         self._input = None
@@ -112,7 +113,11 @@ class GICPEngine:
         return rc
 
     def _push_params(self):
-        self._check(self._lib.mgicp_set_params(self._h, ctypes.byref(self.params)), "mgicp_set_params")
+        rc = self._lib.mgicp_set_params(self._h, ctypes.byref(self.params))
+        if rc < 0:  # refused: the context keeps its parameters, and so does this object
+            ctypes.memmove(ctypes.byref(self.params), ctypes.byref(self._pushed), ctypes.sizeof(self.params))
+        self._check(rc, "mgicp_set_params")
+        self._pushed = type(self.params).from_buffer_copy(self.params)
 
     # -- pcl::Registration setters -----------------------------------------------------------
     def setMaximumIterations(self, n: int):
@@ -132,6 +137,22 @@ class GICPEngine:
 
     def setRotationEpsilon(self, eps: float):
         self.params.rot_eps = float(eps)
+        self._push_params()
+
+    # -- pcl::GeneralizedIterativeClosestPoint setters ----------------------------------------
+    def setCorrespondenceRandomness(self, k: int):
+        """k_correspondences_: the neighbours of a point's covariance (both clouds' are recomputed)"""
+        self.params.k = int(k)
+        self._push_params()
+
+    def setMaximumOptimizerIterations(self, n: int):
+        """max_inner_iterations_: the BFGS steps (GN: the solves) of one outer iteration"""
+        self.params.max_inner_iter = int(n)
+        self._push_params()
+
+    def setGicpEpsilon(self, eps: float):
+        """gicp_epsilon_: the smallest singular value of every covariance (both clouds' are recomputed)"""
+        self.params.gicp_eps = float(eps)
         self._push_params()
 
     def setSolver(self, solver: int):

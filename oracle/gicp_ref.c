@@ -355,6 +355,9 @@ struct ref_gicp {
     double* mahal;    /* ns x 9 row-major */
     int* corr_src; int* corr_tgt; int m;
     int n_evals;
+    /* evaluations of the last align at a state that differs, in any bit, from the state of the evaluation
+     * before it in the same BFGS run (f and then df at one alpha are two functor calls at one state) */
+    int n_state_evals; int have_last_x; double last_x[6];
     /* moment-form objective (prm.objective == 1): taken at the correspondence transform T0 */
     double mom[MOM_VALS];
     float T0[4][4];
@@ -981,6 +984,11 @@ int ref_set_sum_order(ref_gicp* g, int mode, const uint32_t* perm, size_t n) {
 int ref_fdf_mode_sums(ref_gicp* g, const double x[6], double out14[14]);
 
 static void functor_eval(ref_gicp* g, const double x[6], double* f, double grad[6]) {
+    if (!g->have_last_x || memcmp(g->last_x, x, sizeof(g->last_x)) != 0) {
+        g->n_state_evals++;
+        memcpy(g->last_x, x, sizeof(g->last_x));
+        g->have_last_x = 1;
+    }
     if (g->prm.objective == 1) {
         moments_eval(g, x, f, grad);
         return;
@@ -1404,6 +1412,7 @@ static int estimate_bfgs(ref_gicp* g, float T[4][4]) {
     bfgs_t b;
     memset(&b, 0, sizeof(b));
     b.g = g;
+    g->have_last_x = 0; /* a run of its own: its first evaluation counts as a new state */
     b.sigma = 0.01; b.rho = 0.01; b.tau1 = 9; b.tau2 = 0.05; b.tau3 = 0.5; b.order = 3;
     b.step_size = (g->prm.variant & 16) ? 0.1 : 1;
     b.bracket_iters = (g->prm.variant & 8) ? 20 : 100;
@@ -1566,6 +1575,7 @@ int ref_align(ref_gicp* g, const float guess_cm[16], float out_T_cm[16], ref_res
     identity4(prev);
     alloc_scratch(g);
     g->n_evals = 0;
+    g->n_state_evals = 0;
     /* output = input (w = 1); transformPointCloud(output, output, guess) */
     for (int i = 0; i < g->ns; ++i) xform(G, g->src + 3 * (size_t)i, g->out + 3 * (size_t)i);
 
@@ -1615,6 +1625,8 @@ int ref_align(ref_gicp* g, const float guess_cm[16], float out_T_cm[16], ref_res
     if (res) *res = r;
     return REF_OK;
 }
+
+int ref_state_evals(const ref_gicp* g) { return g ? g->n_state_evals : REF_E_INVALID; }
 
 int ref_fitness(ref_gicp* g, const float T_cm[16], double max_range, double* out) {
     if (!g || !out) return REF_E_INVALID;

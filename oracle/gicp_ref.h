@@ -82,6 +82,11 @@ int       ref_set_target(ref_gicp* g, const float* xyz, size_t n, size_t stride_
  * transformation_ after every outer iteration (column-major). */
 int       ref_align(ref_gicp* g, const float guess_cm[16], float out_T_cm[16], ref_result* res,
                     float* trace);
+/* Of the last ref_align's n_evals functor calls, those at a state that differs in some bit from the state
+ * of the call before it in the same BFGS run (each run's first call counts).  PCL's line search asks for f
+ * and then, where the step passes the sufficient-decrease test, for df at the same alpha: two calls, one
+ * state.  This is the count an engine that keeps the last state's f and gradient has to evaluate. */
+int       ref_state_evals(const ref_gicp* g);
 /* Registration::getFitnessScore(max_range) for the final transform T. */
 int       ref_fitness(ref_gicp* g, const float T_cm[16], double max_range, double* out);
 

@@ -76,6 +76,7 @@ def load():
         "ref_set_source": (ctypes.c_int, [P, P, sz, sz]),
         "ref_set_target": (ctypes.c_int, [P, P, sz, sz]),
         "ref_align": (ctypes.c_int, [P, FP, FP, ctypes.POINTER(RefResult), FP]),
+        "ref_state_evals": (ctypes.c_int, [P]),
         "ref_fitness": (ctypes.c_int, [P, FP, ctypes.c_double, DP]),
         "ref_covariances": (ctypes.c_int, [P, sz, sz, ctypes.c_int, ctypes.c_double, ctypes.c_int, DP]),
         "ref_knn": (ctypes.c_int, [P, sz, sz, P, sz, ctypes.c_int, IP, FP]),
@@ -172,6 +173,7 @@ class RefGICP:
         rc = self.lib.ref_align(self.h, _fp(g), _fp(out), ctypes.byref(res), _fp(trace) if want_trace else None)
         info = {k: getattr(res, k) for k, _ in RefResult._fields_}
         info["rc"] = rc
+        info["n_state_evals"] = self.lib.ref_state_evals(self.h)  # gicp_ref.h: functor calls at a new state
         if want_trace:
             it = res.iterations
             info["trace"] = [from_cm(trace[16 * i:16 * i + 16]) for i in range(it)]
