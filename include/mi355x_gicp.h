@@ -99,7 +99,11 @@ int         mgicp_device_count(int* n);
  * Host buffers are copied at call time; the cloud is marked dirty so the next align()
  * rebuilds its grid and covariances (PCL resets its trees/covariances the same way).
  * The *_device variants take a device pointer already resident in HBM on this context's
- * device (no H2D copy). */
+ * device (no H2D copy).  Device buffers are copied at call time too: the engine packs the xyz
+ * into its own storage before the call returns, never writes to the caller's buffer and never
+ * reads it again, so the caller may overwrite or free it afterwards.  The pointer needs float
+ * (4-byte) alignment only.  n = 0, a NULL pointer or a stride below 12 or not a multiple of 4
+ * returns MGICP_E_INVALID before anything is launched. */
 int mgicp_set_target(mgicp_ctx* ctx, const float* xyz, size_t n, size_t stride_bytes);
 int mgicp_set_source(mgicp_ctx* ctx, const float* xyz, size_t n, size_t stride_bytes);
 int mgicp_set_target_device(mgicp_ctx* ctx, const float* d_xyz, size_t n, size_t stride_bytes);
@@ -117,12 +121,19 @@ int mgicp_fitness(mgicp_ctx* ctx, const float T_cm[16], double max_range, double
 
 /* pcl::transformPointCloud(source, out, T) for the xyz fields (GICPAlignment.cpp:144-147):
  * writes n transformed xyz triples into out (record stride out_stride_bytes), leaving the
- * other bytes of each record untouched. */
+ * other bytes of each record untouched.  Each coordinate is ((T_r0 x + T_r1 y) + T_r2 z) + T_r3 in
+ * float without FMA contraction; the last row of T is not read.  Every record goes through that
+ * formula, non-finite ones included: NaN propagates and 0 * Inf = NaN.  (PCL skips non-finite
+ * points of a non-dense cloud and leaves them as they are; this call does not -- that is the
+ * contract.)  out_stride_bytes below 12 or not a multiple of 4: MGICP_E_INVALID. */
 int mgicp_transform_source(mgicp_ctx* ctx, const float T_cm[16], float* out, size_t out_stride_bytes);
 
 /* pcl::transformPointCloud(in, out, T) for any cloud (GICPAlignment::applyTFtoCloud,
  * src/GICPAlignment.cpp:144-147): xyz of n records of `in` are transformed on the GPU and
- * written into `out` (other bytes of the out records untouched; in == out allowed). */
+ * written into `out` (other bytes of the out records untouched; in == out allowed: `in`
+ * is read whole before `out` is written).  The same float formula as mgicp_transform_source, applied to every record: NaN
+ * propagates and 0 * Inf = NaN, where PCL would skip the non-finite points of a non-dense cloud.
+ * Either stride below 12 or not a multiple of 4: MGICP_E_INVALID; n = 0: OK. */
 int mgicp_transform_cloud(mgicp_ctx* ctx, const float T_cm[16], const float* in, size_t n,
                           size_t in_stride_bytes, float* out, size_t out_stride_bytes);
 
@@ -345,7 +356,9 @@ int mgicp_segment_differences(mgicp_ctx* ctx, const float T_cm[16], const float*
  * as floats and truncated (CentroidPoint); leaves with fewer than min_points_per_voxel points are
  * dropped; non-finite records skipped.  `out` holds up to n records of out_stride bytes: x, y, z
  * at 0/4/8, 1.0f at 12 (out_stride >= 16), the colour word at rgb_offset, other bytes zero.  When
- * div_x*div_y*div_z exceeds INT32_MAX PCL warns and returns the input: so does this call. */
+ * div_x*div_y*div_z exceeds INT32_MAX PCL warns and returns the input: so does this call.
+ * rgb_offset is -1 or a multiple of 4 from 12 up that fits both strides; 0, 4 and 8 lie over
+ * x, y, z and return MGICP_E_INVALID, as does any other value. */
 int mgicp_voxel_grid(mgicp_ctx* ctx, const float* in, size_t n, size_t stride, int rgb_offset,
                      const double leaf[3], int min_points_per_voxel, float* out, size_t out_stride,
                      size_t* n_out);

@@ -77,7 +77,7 @@ int aux_grid(mgicp_ctx* ctx, const float* xyz, size_t n, size_t stride, double f
 extern "C" {
 
 int mgicp_transform_source(mgicp_ctx* ctx, const float T_cm[16], float* out, size_t out_stride) {
-  if (!ctx || !T_cm || !out || out_stride < 12 || ctx->src.n == 0) return MGICP_E_INVALID;
+  if (!ctx || !T_cm || !out || out_stride < 12 || (out_stride % 4) || ctx->src.n == 0) return MGICP_E_INVALID;
   HIPCK(hipSetDevice(ctx->device));
   return xform_to_host(ctx, ctx->src.orig.p, ctx->src.n, T_cm, out, out_stride);
 }
@@ -641,8 +641,9 @@ int mgicp_euclidean_clusters(mgicp_ctx* ctx, const float* xyz, size_t n, size_t 
 int mgicp_voxel_grid(mgicp_ctx* ctx, const float* in, size_t n, size_t stride, int rgb_offset,
                      const double leaf[3], int min_points_per_voxel, float* out, size_t out_stride,
                      size_t* n_out) {
+  // a colour word at offset 0, 4 or 8 would lie over x, y or z of every record, read and written
   if (!ctx || !n_out || !leaf || (n && (!in || !out)) || out_stride < 12 || (out_stride % 4) ||
-      (rgb_offset >= 0 && (static_cast<size_t>(rgb_offset) + 4 > stride ||
+      (rgb_offset >= 0 && (rgb_offset < 12 || static_cast<size_t>(rgb_offset) + 4 > stride ||
                            static_cast<size_t>(rgb_offset) + 4 > out_stride || (rgb_offset % 4))))
     return MGICP_E_INVALID;
   for (int d = 0; d < 3; ++d)
