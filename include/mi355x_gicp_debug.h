@@ -91,6 +91,12 @@ int mgicp_debug_kernel_times(mgicp_ctx* ctx, double out_ms[MGICP_KERNEL_FAMILIES
  * evaluations answered without a pass: their fp32 transform had been passed over in the same BFGS
  * run (debug option "pass_memo"), so [1] + [2] - [3] + [8] is what n_evals would be without */
 int mgicp_debug_pass_stats(mgicp_ctx* ctx, long long out[9]);
+/* correspondence rounds of the BFGS mode since mgicp_create (debug option "round_fast"): [0] fast rounds
+ * -- a fused listed sweep whose counters came back zero, so nothing followed its query kernel -- [1] slow
+ * rounds (every other round: cold or unfused sweeps, and fused ones with work left), [2] fused rounds
+ * that deferred chunks to the compaction launch, [3] fused rounds that left queries pending.  [2] and
+ * [3] are known only where the counters are read, i.e. with "round_fast" 1. */
+int mgicp_debug_round_stats(mgicp_ctx* ctx, long long out[4]);
 /* the resident pass server as the aligns run it (always on, two HIP events per server launch on the
  * engine's stream, resolved when an align drains): *out_ms = summed device duration of the server
  * launches (first command .. cancel, host round trips between passes included), *out_passes = the

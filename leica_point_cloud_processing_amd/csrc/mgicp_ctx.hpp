@@ -288,6 +288,8 @@ struct mgicp_ctx {
   unsigned long long* d_rows = nullptr;
   size_t rows_cap = 0;                  // supers per parity buffer
   std::vector<double> row_sums;         // decoded super partials
+  bool rows_running = true;             // debug option "rows_running": single rank, the total's lane sums are taken
+                                        // while the rows land (shm::RunningTotal; 0: fixed_total after the last row)
   unsigned int pass_idx = 0;            // objective passes so far: the row stamp (identical on every rank)
   unsigned long long gather_idx = 0;    // generic gathers through the shared segment so far
   // node-wide transport (mgicp_comm_attach_shm)
@@ -369,6 +371,17 @@ struct mgicp_ctx {
   bool vlist = true;
   bool fuse_compact = true;           // r04: compaction fused into listed sweeps (debug option "fuse_compact")
   DevBuf<uint32_t> vl_defer;          // chunks a fused sweep deferred to the compaction launch
+  // r08, the steady-state round (DESIGN.md "r08: the steady-state round"): a fused listed sweep hands
+  // ctr[1..3] to the host (one wave, stamped words in mapped memory); all zero = nothing was requested,
+  // left pending or deferred, so centres, builds, fallback, the lazy-covariance pass and the deferred
+  // compaction are not launched at all (debug option "round_fast" 0: always launched, as before r08)
+  bool round_fast = true;
+  unsigned long long* h_round = nullptr;   // 3 words (stamp << 32) | ctr[1 + i]; host / device views
+  unsigned long long* d_round = nullptr;
+  unsigned int round_stamp = 0;            // the last round's stamp (never 0)
+  const unsigned int* vl_ctr_zero = nullptr;  // == vl_ctr.p while ctr[1..4] are known to be zero (a clean round
+                                              // left them so): the next sweep does not fill them again
+  long long round_st[4] = {0, 0, 0, 0};    // mgicp_debug_round_stats
   bool vl_stats = false;              // debug option "vlist_stats": per-sweep list diagnostics on stderr
   bool vl_valid = false;              // lists belong to the current target grid and gate
   bool vl_alloc = false;              // their state words and pool are allocated and initialised
@@ -513,11 +526,13 @@ struct ProfScope {
       (void)hipEventRecord(a, ctx->stream);
     }
   }
-  ~ProfScope() {
+  ~ProfScope() { close(); }
+  void close() {  // ends the scope early (once)
     if (a) {
       hipEvent_t b = ev_get(ctx);
       (void)hipEventRecord(b, ctx->stream);
       ctx->pending.push_back({a, b, fam});
+      a = nullptr;
     }
   }
 };

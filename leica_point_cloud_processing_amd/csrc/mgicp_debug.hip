@@ -24,6 +24,12 @@ int mgicp_debug_pass_stats(mgicp_ctx* ctx, long long out[9]) {
   return MGICP_OK;
 }
 
+int mgicp_debug_round_stats(mgicp_ctx* ctx, long long out[4]) {
+  if (!ctx || !out) return MGICP_E_INVALID;
+  for (int i = 0; i < 4; ++i) out[i] = ctx->round_st[i];
+  return MGICP_OK;
+}
+
 int mgicp_debug_server_time(mgicp_ctx* ctx, double* out_ms, long long* out_passes, long long* out_launches,
                             int reset) {
   if (!ctx || !out_ms || !out_passes || !out_launches) return MGICP_E_INVALID;
@@ -548,6 +554,8 @@ int mgicp_debug_option(mgicp_ctx* ctx, const char* name, double value) {
     ctx->vl_valid = false;
   } else if (n == "vlist_stats") ctx->vl_stats = on;    // per-sweep list statistics on stderr
   else if (n == "fuse_compact") ctx->fuse_compact = on; // compaction fused into listed sweeps
+  else if (n == "round_fast") ctx->round_fast = on;     // r08: a clean fused sweep ends its round (0: every follow-up launched)
+  else if (n == "rows_running") ctx->rows_running = on; // r08: single rank, the row total taken while the rows land
   else if (n == "target_cache") ctx->tcache_on = on;    // adopt / leave the target state (process cache)
   else if (n == "match_pairs_per_launch")               // mgicp_match_features: pairs of one launch (0: the default)
     ctx->match_pairs_per_launch = value >= 1.0 ? static_cast<unsigned long long>(std::min(value, 9.0e18)) : kMatchPairsPerLaunch;

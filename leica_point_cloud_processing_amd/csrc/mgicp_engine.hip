@@ -166,6 +166,7 @@ hipError_t launch_sweep(mgicp_ctx* ctx, const Mat4& T, double thr, bool seeded, 
                         const FusedCompact* fc = nullptr) {
   const size_t p0 = ctx->shard_p0(), p1 = ctx->shard_p1();
   const GridView& g = ctx->tgt.view;
+  if (sweep_listed(ctx)) ctx->vl_ctr_zero = nullptr;  // this sweep fills the counters and may leave them non-zero
   if (sweep_listed(ctx))
     return launch_vl_sweep(g, ctx->vl, ctx->d_out, p0, p1, T.xf(), thr, seeded ? 1 : 0, ctx->prev_pos.p, ctx->flags.p,
                            ctx->cus, ctx->stream, fc);
@@ -236,6 +237,29 @@ int report_sweep(mgicp_ctx* ctx) {
                  st[7], (st[0] + 63) / 64, st[7] ? double(st[6]) / st[7] : 0.0);
   }
 #endif
+  return MGICP_OK;
+}
+
+// r08: the verdict of the fused listed sweep stamped `stamp` (vl_round_publish_kernel): spin on the three
+// mapped words as wait_pass does on its completion word; after ~0.5 s fall back to a stream drain so a
+// failed launch surfaces as an error instead of a hang.  c = ctr[1..3]: requested, pending, deferred.
+int wait_round(mgicp_ctx* ctx, unsigned int stamp, unsigned int c[3]) {
+  auto take = [&]() {
+    for (int i = 0; i < 3; ++i) {
+      const unsigned long long w = __atomic_load_n(ctx->h_round + i, __ATOMIC_ACQUIRE);
+      if (static_cast<unsigned int>(w >> 32) != stamp) return false;
+      c[i] = static_cast<unsigned int>(w);
+    }
+    return true;
+  };
+  const auto t0 = std::chrono::steady_clock::now();
+  for (unsigned spins = 0;; ++spins) {
+    if (take()) return MGICP_OK;
+    if ((spins & 1023u) == 1023u && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(500)) break;
+  }
+  int rc = sync(ctx);
+  if (rc) return rc;
+  if (!take()) return fail(ctx, MGICP_E_HIP, "listed sweep finished without publishing its round counters");
   return MGICP_OK;
 }
 
@@ -507,13 +531,43 @@ int mgicp::correspond(mgicp_ctx* ctx, const Mat4& T, const Mat4& G, bool seed) {
     fc.defer = ctx->vl_defer.p;
     fc.out = corr_soa(ctx);
   }
+  // r08: a fused listed sweep queues its queries alone and hands ctr[1..3] to the host.  All zero: no cell
+  // was requested, no query is pending and no chunk was deferred (a chunk is deferred exactly when it
+  // holds a pending query or an accepted point without a covariance), so the streams are complete and
+  // everything from vl_centre_kernel to the deferred compaction would find nothing to do.  Otherwise,
+  // and for every other sweep, the sequence is the one before r08.  The decision is this rank's alone.
+  const bool fast = fused && ctx->round_fast && ctx->h_round && ns > 0;
+  bool clean = false;
+  unsigned int c3[3] = {0, 0, 0};
   {
     ProfScope ps(ctx, kFamCorr);
-    HIPCK(launch_sweep(ctx, T, thr, seeded, qp, fused ? &fc : nullptr));
+    if (fast) {
+      if (++ctx->round_stamp == 0) ctx->round_stamp = 1;
+      const bool zero_ctr = ctx->vl_ctr_zero != ctx->vl_ctr.p;
+      ctx->vl_ctr_zero = nullptr;
+      HIPCK(launch_vl_queries(ctx->vl, ctx->d_out, p0, p1, T.xf(), thr, ctx->prev_pos.p, ctx->flags.p, s, &fc, zero_ctr,
+                              ctx->d_round, ctx->round_stamp));
+      if (int rc = wait_round(ctx, ctx->round_stamp, c3)) return rc;
+      clean = !(c3[0] | c3[1] | c3[2]);
+      if (clean)
+        ctx->vl_ctr_zero = ctx->vl_ctr.p;  // ctr[4] is written by the builds only: still zero from the last fill
+      else
+        HIPCK(launch_vl_follow(ctx->tgt.view, ctx->vl, ctx->d_out, p0, p1, T.xf(), thr, seeded ? 1 : 0, ctx->prev_pos.p,
+                               ctx->flags.p, ctx->cus, s));
+    } else {
+      HIPCK(launch_sweep(ctx, T, thr, seeded, qp, fused ? &fc : nullptr));
+    }
   }
   ctx->seed_valid = true;
   MGICP_TRACE_AT("corr: sweep queued");
   if (int rc = report_sweep(ctx)) return rc;
+  ctx->round_st[clean ? 0 : 1]++;
+  if (c3[2]) ctx->round_st[2]++;
+  if (c3[1]) ctx->round_st[3]++;
+  if (clean) {
+    ctx->have_corr = true;
+    return MGICP_OK;
+  }
   {
     int rc = cov_join_all(ctx);  // set_target's / set_source's covariances (they ran beside this sweep)
     if (rc) return rc;
@@ -753,6 +807,7 @@ void mgicp_destroy(mgicp_ctx* ctx) {
   if (ctx->mail) (void)hipFree(ctx->mail);
   if (ctx->h_red) (void)hipHostFree(ctx->h_red);
   if (ctx->h_cmd) (void)hipHostFree(ctx->h_cmd);
+  if (ctx->h_round) (void)hipHostFree(ctx->h_round);
   if (ctx->h_gtrace) (void)hipHostFree(ctx->h_gtrace);
   if (ctx->h_ptimes) (void)hipHostFree(ctx->h_ptimes);
   if (ctx->h_rows) (void)hipHostFree(ctx->h_rows);

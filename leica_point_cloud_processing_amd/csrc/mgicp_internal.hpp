@@ -204,6 +204,17 @@ struct FusedCompact {
 hipError_t launch_vl_sweep(const GridView& tgt, const VListView& vl, const float4* src, size_t p0, size_t p1,
                            Xf34 T, double thr, int seeded, uint32_t* nn_pos, uint32_t* flags, int cus,
                            hipStream_t s, const FusedCompact* fc = nullptr);
+// r08, the sweep in its two halves (launch_vl_sweep = both, counters zeroed, no verdict).
+// launch_vl_queries: the query kernel alone; zero_ctr false when ctr[1..4] are known to be zero (the
+// round before was clean); verdict (mapped host memory, 3 words) non-null: one wave then stores
+// (stamp << 32) | ctr[1 + i] into verdict[i].  launch_vl_follow: centres, the two builds, the fallback --
+// every one of them a no-op when ctr[1] == ctr[2] == 0.
+hipError_t launch_vl_queries(const VListView& vl, const float4* src, size_t p0, size_t p1, Xf34 T, double thr,
+                             uint32_t* nn_pos, uint32_t* flags, hipStream_t s, const FusedCompact* fc, bool zero_ctr,
+                             unsigned long long* verdict, unsigned int stamp);
+hipError_t launch_vl_follow(const GridView& tgt, const VListView& vl, const float4* src, size_t p0, size_t p1,
+                            Xf34 T, double thr, int seeded, uint32_t* nn_pos, uint32_t* flags, int cus,
+                            hipStream_t s);
 // lazy source covariances (r04): shard positions k with flags[k] && !cov_ok[k] -> list (absolute
 // positions p0 + k, *count of them), cov_ok[k] = 1
 hipError_t launch_cov_need(const uint32_t* flags, uint8_t* cov_ok, size_t p0, size_t n, uint32_t* list,

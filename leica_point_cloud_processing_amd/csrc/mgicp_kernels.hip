@@ -1822,6 +1822,18 @@ __global__ __launch_bounds__(256, 6) void vl_query_compact_kernel(VListView v, c
   }
 }
 
+// r08: the sweep's verdict for the host.  One wave behind vl_query_compact_kernel copies ctr[1..3]
+// (cells requested, queries pending, chunks deferred) into mapped host memory, each as one 8-byte word
+// (stamp << 32) | count: a word is valid as soon as it carries the round's stamp, so no flag follows
+// and no store has to be ordered against another.
+__global__ __launch_bounds__(64) void vl_round_publish_kernel(unsigned int* ctr, unsigned long long* host_words,
+                                                              unsigned int stamp) {
+  if (threadIdx.x >= 3) return;
+  const unsigned int c = __hip_atomic_load(ctr + 1 + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_store(host_words + threadIdx.x, (static_cast<unsigned long long>(stamp) << 32) | c, __ATOMIC_RELAXED,
+                     __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 // the requested cells' centres: exact 1-NN within sqrt(thr_c) (none: every point is farther than the
 // gate from the whole cell -> reject)
 __global__ __launch_bounds__(256) void vl_centre_kernel(GridView tg, VListView v, double thr_c) {
@@ -4677,15 +4689,32 @@ hipError_t launch_knn_cov(const GridView& g, int k, double eps, size_t p0, size_
 hipError_t launch_vl_sweep(const GridView& tgt, const VListView& vl, const float4* src, size_t p0, size_t p1,
                            Xf34 T, double thr, int seeded, uint32_t* nn_pos, uint32_t* flags, int cus,
                            hipStream_t s, const FusedCompact* fc) {
+  hipError_t e = launch_vl_queries(vl, src, p0, p1, T, thr, nn_pos, flags, s, fc, true, nullptr, 0);
+  return e != hipSuccess ? e : launch_vl_follow(tgt, vl, src, p0, p1, T, thr, seeded, nn_pos, flags, cus, s);
+}
+
+hipError_t launch_vl_queries(const VListView& vl, const float4* src, size_t p0, size_t p1, Xf34 T, double thr,
+                             uint32_t* nn_pos, uint32_t* flags, hipStream_t s, const FusedCompact* fc, bool zero_ctr,
+                             unsigned long long* verdict, unsigned int stamp) {
   if (p1 <= p0) return hipSuccess;
-  hipError_t e = hipMemsetAsync(vl.ctr + 1, 0, 4 * sizeof(unsigned int), s);
-  if (e != hipSuccess) return e;
+  if (zero_ctr) {
+    hipError_t e = hipMemsetAsync(vl.ctr + 1, 0, 4 * sizeof(unsigned int), s);
+    if (e != hipSuccess) return e;
+  }
   if (fc)
     vl_query_compact_kernel<<<chunk_count(p1 - p0), 256, 0, s>>>(vl, src, p0, p1 - p0, T, thr, nn_pos, flags, fc->cov_s,
                                                                   fc->cov_t, fc->R, fc->cov_ok, fc->ccnt, fc->defer,
                                                                   fc->out);
   else
     vl_query_kernel<<<nblk(p1 - p0), 256, 0, s>>>(vl, src, p0, p1 - p0, T, thr, nn_pos, flags);
+  if (verdict) vl_round_publish_kernel<<<1, 64, 0, s>>>(vl.ctr, verdict, stamp);
+  return hipGetLastError();
+}
+
+hipError_t launch_vl_follow(const GridView& tgt, const VListView& vl, const float4* src, size_t p0, size_t p1,
+                            Xf34 T, double thr, int seeded, uint32_t* nn_pos, uint32_t* flags, int cus,
+                            hipStream_t s) {
+  if (p1 <= p0) return hipSuccess;
   // requested cells: the centre's 1-NN within the gate + the grown cell's half diagonal, then the lists
   const double hd = std::sqrt(3.0) * (0.5 * static_cast<double>(vl.c) + static_cast<double>(vl.es));
   const double rc = vl.gate * (1.0 + 1e-5) + 1e-9 + hd;
@@ -5508,6 +5537,7 @@ hipError_t preload_kernels(void* pinned, size_t pinned_bytes, hipStream_t s) {
       reinterpret_cast<const void*>(&chunk_compact_kernel),
       reinterpret_cast<const void*>(&chunk_compact_list_kernel),
       reinterpret_cast<const void*>(&vl_query_compact_kernel),
+      reinterpret_cast<const void*>(&vl_round_publish_kernel),
       reinterpret_cast<const void*>(&fdf_soa_kernel),
       reinterpret_cast<const void*>(&fdf_soa_gated_kernel),
       reinterpret_cast<const void*>(&fdf_server_kernel<false, kSrvWaves>),

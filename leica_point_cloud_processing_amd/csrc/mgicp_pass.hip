@@ -546,6 +546,12 @@ int mgicp::ensure_host_red(mgicp_ctx* ctx) {
     }
 #endif
   }
+  if (!ctx->h_round) {  // r08: the listed sweep's verdict words (stamp 0 is never a round's stamp)
+    HIPCK(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_round), 8 * sizeof(unsigned long long),
+                        hipHostMallocMapped | hipHostMallocCoherent));
+    HIPCK(hipHostGetDevicePointer(reinterpret_cast<void**>(&ctx->d_round), ctx->h_round, 0));
+    std::memset(ctx->h_round, 0, 8 * sizeof(unsigned long long));
+  }
   if (ctx->h_red) return MGICP_OK;
   // kRedVals sums followed by the pass-completion word (see launch_fdf_soa's done_flag)
   HIPCK(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_red), 2 * kRedVals * sizeof(double),
@@ -644,9 +650,21 @@ int mgicp::wait_rows(mgicp_ctx* ctx, unsigned int rstamp, const Xf34& A, double 
     shm::row_decode(reinterpret_cast<const uint64_t*>(row), &ctx->row_sums[static_cast<size_t>(r) * kRedVals]);
     return MGICP_OK;
   };
+  // r08, single rank: the lanes' sums are taken while the later rows are still on their way (rows are
+  // waited for in index order, which is the order fixed_total adds them in); any other row view keeps
+  // fixed_total
+  static_assert(shm::RunningTotal::kVals == kRedVals, "RunningTotal restates the pass's value count");
+  const bool running = ctx->rows_running && rv.first == 0 && rv.nloc == rv.ntot;
+  shm::RunningTotal rt;
+  if (running) rt.reset();
   for (long long r = rv.first; r < rv.first + rv.nloc; ++r) {
     int rc = wait_row(r, true);
     if (rc) return rc;
+    if (running) rt.add_row(r, &ctx->row_sums[static_cast<size_t>(r) * kRedVals]);
+  }
+  if (running) {
+    rt.finish(out);
+    return MGICP_OK;
   }
   t0 = std::chrono::steady_clock::now();
   for (long long r = 0; r < rv.ntot; ++r) {

@@ -232,6 +232,33 @@ inline void fixed_total(const double* rows, long long nsup, int nv, double* out)
   }
 }
 
+// r08: fixed_total for 16 values, taken while the rows land.  Lane l's partial (supers l, l + 64, ... in
+// order, from +0.0) is final once its rows are in, and a host that waits for the rows in index order
+// can add each one as it arrives: only finish()'s 63-step tree is left for after the last row.
+// add_row must be called with r = 0, 1, 2, ... (each lane then sees its supers in fixed_total's
+// order).  Every lane starts from +0.0 and the row is ADDED to it, so a -0.0 first row gives +0.0 as
+// fixed_total's a = 0.0; a += row does, and lanes without a row stay +0.0.  Lanes are laid out
+// [lane][value]: the 16 additions of a step are independent and contiguous.  Plain additions only; the
+// result is fixed_total's bit for bit (tests/running_total_standalone).
+struct RunningTotal {
+  static constexpr int kVals = 16;
+  alignas(64) double lanes[64][kVals];
+  void reset() {
+    for (int l = 0; l < 64; ++l)
+      for (int v = 0; v < kVals; ++v) lanes[l][v] = 0.0;
+  }
+  void add_row(long long r, const double* sums) {
+    double* a = lanes[r & 63];
+    for (int v = 0; v < kVals; ++v) a[v] = a[v] + sums[v];
+  }
+  void finish(double* out) {  // consumes the lanes: reset() before the next total
+    for (int off = 32; off > 0; off >>= 1)
+      for (int i = 0; i < off; ++i)
+        for (int v = 0; v < kVals; ++v) lanes[i][v] = lanes[i][v] + lanes[i + off][v];
+    for (int v = 0; v < kVals; ++v) out[v] = lanes[0][v];
+  }
+};
+
 // Generic gather, step 2: after this rank's rows of gather g are in gath(g & 1) (caller), publish g
 // and wait until every rank has published g.  false on timeout.
 inline bool gather_publish_wait(const Segment& s, uint64_t g, double timeout_s) {

@@ -450,6 +450,14 @@ class GICPEngine:
         self._check(self._lib.mgicp_debug_pass_stats(self._h, out), "pass_stats")
         return {k: int(out[i]) for i, k in enumerate(self.PASS_STATS)}
 
+    ROUND_STATS = ("fast", "slow", "deferred", "pending")
+
+    def round_stats(self) -> dict:
+        """Correspondence rounds of the BFGS mode (mgicp_debug_round_stats)."""
+        out = (ctypes.c_longlong * len(self.ROUND_STATS))()
+        self._check(self._lib.mgicp_debug_round_stats(self._h, out), "round_stats")
+        return {k: int(out[i]) for i, k in enumerate(self.ROUND_STATS)}
+
     def server_time(self, reset: bool = False) -> dict:
         """The resident pass server as the aligns run it (mgicp_debug_server_time): summed launch
         duration, passes and launches since the last reset; ms_per_pass = the in-align pass."""
