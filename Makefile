@@ -12,7 +12,8 @@ LDMAP := -Wl,--version-script=$(MAP)
 # -ffp-contract=off: no FMA contraction, so fp32/fp64 expressions round like PCL's SSE2 Eigen
 HIPFLAGS := -O3 -std=c++17 --offload-arch=$(ARCH) -fPIC -ffp-contract=off -Wall -Wno-unused-result
 
-all: $(LIB) oracle adapter-example adapter-replay fod-replay normals-replay boundary-replay fpfh-replay corr-replay
+all: $(LIB) oracle adapter-example adapter-replay fod-replay normals-replay boundary-replay fpfh-replay corr-replay \
+     harris-replay
 
 OBJDIR := $(PKG)/csrc/build
 OBJS  := $(OBJDIR)/mgicp_kernels.o $(OBJDIR)/mgicp_engine.o $(OBJDIR)/mgicp_clouds.o $(OBJDIR)/mgicp_pass.o \
@@ -129,6 +130,22 @@ $(CORRREPLAY): adapter/InitialAlignment_correspondences_mi355x.cpp include/mi355
 
 corr-replay: $(CORRREPLAY)
 
+# adapter/InitialAlignment_harris_mi355x.cpp (InitialAlignment::obtainHarrisKeypoints) compiled the same way:
+# the InitialAlignment.h and Filter.h of tests/adapter_standins_harris in front (the class with that private
+# member and its radius_factor_; Filter::extractIndices, which the member ends in), linked with a driver that
+# calls it on a cloud file and a normals file (test infrastructure)
+STANDIN_HAR := tests/adapter_standins_harris
+HARREPLAY   := adapter/build/replay_test_harris
+$(HARREPLAY): adapter/InitialAlignment_harris_mi355x.cpp include/mi355x_gicp.h $(wildcard $(STANDIN)/*.h) \
+              $(wildcard $(STANDIN_NRM)/*.h) $(wildcard $(STANDIN_HAR)/*.h) $(STANDIN)/Utils_standin.cpp \
+              $(STANDIN_HAR)/replay_test_harris.cpp $(LIB)
+	mkdir -p adapter/build
+	g++ -O2 -std=c++14 -Wall -Wextra -Werror -I$(STANDIN_HAR) -I$(STANDIN_NRM) -I$(STANDIN) -Iadapter -Iinclude -o $@ \
+	    adapter/InitialAlignment_harris_mi355x.cpp $(STANDIN)/Utils_standin.cpp $(STANDIN_HAR)/replay_test_harris.cpp \
+	    -L$(PKG) -lmgicp -Wl,-rpath,'$$ORIGIN/../../$(PKG)'
+
+harris-replay: $(HARREPLAY)
+
 oracle:
 	$(MAKE) -C oracle
 
@@ -136,4 +153,4 @@ clean:
 	rm -f $(LIB) $(PKG)/libmgicp_*.so $(OBJS)
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle clean adapter-example adapter-replay fod-replay normals-replay boundary-replay fpfh-replay corr-replay variant
+.PHONY: all oracle clean adapter-example adapter-replay fod-replay normals-replay boundary-replay fpfh-replay corr-replay harris-replay variant

@@ -231,6 +231,57 @@ int mgicp_boundary_points(mgicp_ctx* ctx, const float* xyz, size_t n, size_t str
                           int* nn_indices /* may be NULL, n * k */,
                           mgicp_boundary_info* info /* may be NULL */);
 
+/* InitialAlignment::obtainHarrisKeypoints (src/InitialAlignment.cpp:399-424; the HARRIS method calls it on
+ * both clouds after getNormals): pcl::HarrisKeypoint3D<PointXYZRGB, PointXYZI> with its default method
+ * HARRIS, setNonMaxSupression(true), setThreshold(1e-6), setRadius(radius_factor_ * resolution), refine off;
+ * PCL 1.8.1 harris_3d.hpp (detectKeypoints, calculateNormalCovar, responseHarris) restated [PCL].  PCL is
+ * not available to this project's tests, so parity with PCL binaries is unpinned (README "Parity"); the
+ * rules below are the contract, and every deviation from PCL in them is deliberate.
+ * Neighbour set N(i) of a finite record i: every finite record j, i included, with FLANN's float
+ * ((dx^2) + dy^2) + dz^2 < float(radius^2), strict -- the set of mgicp_estimate_normals;
+ * n_neighbors[i] = |N(i)| (exact; 0 for a non-finite record).  Non-finite records are in no set.
+ * Normal moments (calculateNormalCovar): c_i = the members of N(i) whose normal_x is finite (PCL tests x
+ * alone: a NaN or Inf in another component goes through the sums); for each of them the six products
+ * nx nx, nx ny, nx nz, ny ny, ny nz, nz nz, each rounded to float without FMA contraction.  Deviation (a):
+ * the products are summed in fp64 in the engine's own fixed order (ascending grid position on a grid that
+ * depends on the cloud and the radius alone) and covar = (float)(S / (double)c_i) -- PCL adds them in float
+ * in FLANN's order and multiplies by float(1.0 / count).  c_i = 0: six zeros.  covar[i * 6 ..] = xx xy xz
+ * yy yz zz; a non-finite record gets six zeros.
+ * Response (responseHarris), in float without FMA contraction, PCL's expression left to right:
+ * trace = (xx + yy) + zz; if trace != 0,
+ * det = ((((xx yy) zz + ((2 xy) xz) yz) - (xz xz) yy) - (xy xy) zz) - (yz yz) xx and
+ * response = (0.04f + det) - (0.04f trace) trace (the "0.04f +" is PCL's: it quantises det to the ulp of
+ * 0.04, so equal responses are common); otherwise 0.  A non-finite record gets 0.
+ * Keypoints, nonmax != 0: record i iff it is finite, response[i] is finite, !(response[i] < threshold) and
+ * no j in N(i) has response[i] < response[j].  Equal responses keep both records; a NaN neighbour
+ * suppresses nothing.  nonmax == 0: every record 0 .. n - 1 (PCL's branch returns the response cloud), the
+ * second sweep is not run and n_tied is 0.  keypoints: the record indices ascending (deviation (b): PCL's
+ * OpenMP order is not reproduced), *n_keypoints of them, the entries after those set to -1.
+ * normals: x, y, z at byte offsets 0/4/8 of records of normal_stride_bytes (>= 12, a multiple of 4; 32
+ * for pcl::Normal).  float(radius^2) = 0 links nothing: every response is 0 and no record is a keypoint for
+ * a positive threshold.  radius negative or NaN, a NaN threshold, a bad pointer or stride, n > INT32_MAX:
+ * MGICP_E_INVALID; n = 0: OK.  The same bits in every output on every call.
+ * Uses the helper cloud slot: a set source / target and their cached state stay as they are.
+ * Single rank: with a communicator attached it runs locally, without a collective. */
+typedef struct {
+    double n_finite;      /* finite records (the searched tree) */
+    double n_candidates;  /* records with a finite response >= threshold */
+    double n_keypoints;   /* indices written */
+    double n_tied;        /* keypoints whose response is equalled by another member of their set */
+    double pair_tests;    /* point-pair distance evaluations of both sweeps */
+    double ms_grid;       /* host call -> grid of the finite records built (uploads included) */
+    double ms_device;     /* first launch -> stream synchronise after the last */
+    double ms_total;      /* host call -> outputs written */
+} mgicp_harris_info;
+int mgicp_harris_keypoints(mgicp_ctx* ctx, const float* xyz, size_t n, size_t stride_bytes,
+                           const float* normals, size_t normal_stride_bytes,
+                           double radius, float threshold, int nonmax,
+                           int* keypoints /* capacity n, ascending record index */, size_t* n_keypoints,
+                           float* response /* may be NULL, packed n */,
+                           float* covar /* may be NULL, n * 6: xx xy xz yy yz zz */,
+                           int* n_neighbors /* may be NULL, packed n */,
+                           mgicp_harris_info* info /* may be NULL */);
+
 /* InitialAlignment::obtainFeatures (src/InitialAlignment.cpp:487-508; the BOUNDARY and HARRIS methods call it
  * at the keypoint indices, MULTISCALE's estimator is the same over every point):
  * pcl::FPFHEstimation<PointXYZRGB, Normal, FPFHSignature33> with setRadiusSearch(radius_factor_ * resolution);

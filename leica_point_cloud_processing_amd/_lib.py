@@ -91,6 +91,19 @@ class MgicpBoundaryInfo(ctypes.Structure):
     ]
 
 
+class MgicpHarrisInfo(ctypes.Structure):
+    _fields_ = [
+        ("n_finite", ctypes.c_double),
+        ("n_candidates", ctypes.c_double),
+        ("n_keypoints", ctypes.c_double),
+        ("n_tied", ctypes.c_double),
+        ("pair_tests", ctypes.c_double),
+        ("ms_grid", ctypes.c_double),
+        ("ms_device", ctypes.c_double),
+        ("ms_total", ctypes.c_double),
+    ]
+
+
 class MgicpFpfhInfo(ctypes.Structure):
     _fields_ = [
         ("n_finite", ctypes.c_double),
@@ -150,6 +163,8 @@ _SIGNATURES = {
                                                ctypes.POINTER(MgicpNormalsInfo)]),
     "mgicp_boundary_points": (ctypes.c_int, [_P, _P, _SZ, _SZ, _P, _SZ, ctypes.c_int, ctypes.c_double, _P, _P, _P,
                                               ctypes.POINTER(MgicpBoundaryInfo)]),
+    "mgicp_harris_keypoints": (ctypes.c_int, [_P, _P, _SZ, _SZ, _P, _SZ, ctypes.c_double, ctypes.c_float, ctypes.c_int,
+                                               _P, ctypes.POINTER(_SZ), _P, _P, _P, ctypes.POINTER(MgicpHarrisInfo)]),
     "mgicp_fpfh_features": (ctypes.c_int, [_P, _P, _SZ, _SZ, _P, _SZ, _P, _SZ, ctypes.c_double, _P, _SZ, _P, _P,
                                             ctypes.POINTER(MgicpFpfhInfo)]),
     "mgicp_match_features": (ctypes.c_int, [_P, _P, _SZ, _SZ, _P, _SZ, _SZ, ctypes.c_double, _P, _P,

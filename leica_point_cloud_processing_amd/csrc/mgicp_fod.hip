@@ -1,5 +1,5 @@
 // mgicp_fod.hip -- the product calls beside the alignment (include/mi355x_gicp.h): point transforms,
-// cloud resolution, the radius filter, radius normals, boundary points, FPFH descriptors, feature
+// cloud resolution, the radius filter, radius normals, boundary points, Harris keypoints, FPFH descriptors, feature
 // correspondences, segment differences, Euclidean clustering and the voxel grid.
 #pragma clang fp contract(off)
 
@@ -268,6 +268,103 @@ int mgicp_boundary_points(mgicp_ctx* ctx, const float* xyz, size_t n, size_t str
   inf.n_boundary = static_cast<double>(n_boundary);
   inf.n_undecided = static_cast<double>(n_nan - (n - nf));  // every non-finite record has a NaN gap
   inf.pair_tests = static_cast<double>(ntests);
+  inf.ms_grid = t1 - t0;
+  inf.ms_device = t2 - t1;
+  inf.ms_total = now_ms() - t0;
+  if (info) *info = inf;
+  return MGICP_OK;
+}
+
+int mgicp_harris_keypoints(mgicp_ctx* ctx, const float* xyz, size_t n, size_t stride, const float* normals,
+                           size_t normal_stride, double radius, float threshold, int nonmax, int* keypoints,
+                           size_t* n_keypoints, float* response, float* covar, int* n_neighbors,
+                           mgicp_harris_info* info) {
+  if (!ctx || !(radius >= 0) || threshold != threshold || !n_keypoints || (n && (!xyz || !normals || !keypoints)) ||
+      stride < 12 || (stride % 4) || normal_stride < 12 || (normal_stride % 4) || n > size_t(INT32_MAX))
+    return MGICP_E_INVALID;
+  HIPCK(hipSetDevice(ctx->device));
+  const double t0 = now_ms();
+  mgicp_harris_info inf{};
+  if (info) *info = inf;
+  *n_keypoints = 0;
+  if (n == 0) return MGICP_OK;
+  // FLANN's radius: float(radius^2), strict.  0 links nothing, not even a point with itself
+  const float r2 = static_cast<float>(radius * radius);
+  double reach = radius;
+  if (r2 < 1.17549435e-38f) reach = std::max(reach, std::sqrt(static_cast<double>(r2)));
+  // the tree holds the finite records only: grid over those, at a cell edge of one radius
+  int rc = aux_grid(ctx, xyz, n, stride, r2 > 0.f ? std::min(reach, 1e30) : 0.0);
+  if (rc) return rc;
+  const size_t nf = ctx->aux.n;
+  hipStream_t s = ctx->stream;
+  std::vector<float> hn(3 * n);
+  const unsigned char* nbase = reinterpret_cast<const unsigned char*>(normals);
+  for (size_t i = 0; i < n; ++i) std::memcpy(&hn[3 * i], nbase + i * normal_stride, 12);
+  ScopedBuf<float> d_nrm, d_rpos, d_resp, d_cov;
+  ScopedBuf<float4> d_pack;
+  ScopedBuf<int> d_cnt;
+  ScopedBuf<uint32_t> d_flag, d_pos, d_list, d_fb;
+  ScopedBuf<unsigned char> d_scratch;
+  ScopedBuf<unsigned int> d_fbn;
+  ScopedBuf<unsigned long long> d_ctr;
+  const size_t sb = scan_scratch_bytes(n + 1);
+  HIPCK(d_nrm.reserve(3 * n));
+  HIPCK(d_pack.reserve(std::max<size_t>(nf, 1)));
+  HIPCK(d_rpos.reserve(std::max<size_t>(nf, 1)));
+  HIPCK(d_fb.reserve(std::max<size_t>(nf, 1)));
+  if (response) HIPCK(d_resp.reserve(n));
+  if (covar) HIPCK(d_cov.reserve(6 * n));
+  if (n_neighbors) HIPCK(d_cnt.reserve(n));
+  HIPCK(d_flag.reserve(n + 1));
+  HIPCK(d_pos.reserve(n + 1));
+  HIPCK(d_list.reserve(n));
+  HIPCK(d_scratch.reserve(sb));
+  HIPCK(d_fbn.reserve(1));
+  HIPCK(d_ctr.reserve(3 * kHarCtrSlots));
+  HIPCK(hipMemcpyAsync(d_nrm.p, hn.data(), 3 * n * sizeof(float), hipMemcpyHostToDevice, s));
+  if ((rc = sync(ctx))) return rc;
+  const double t1 = now_ms();
+  // records outside the grid (non-finite) keep these: response 0, covar 0, no neighbour, no flag; list
+  // entries past the count stay -1
+  if (response) HIPCK(hipMemsetAsync(d_resp.p, 0, n * sizeof(float), s));
+  if (covar) HIPCK(hipMemsetAsync(d_cov.p, 0, 6 * n * sizeof(float), s));
+  if (n_neighbors) HIPCK(hipMemsetAsync(d_cnt.p, 0, n * sizeof(int), s));
+  HIPCK(hipMemsetAsync(d_flag.p, 0, (n + 1) * sizeof(uint32_t), s));
+  HIPCK(hipMemsetAsync(d_list.p, 0xff, n * sizeof(uint32_t), s));
+  HIPCK(hipMemsetAsync(d_ctr.p, 0, 3 * kHarCtrSlots * sizeof(unsigned long long), s));
+  const GridView& g = ctx->aux.view;
+  // 1. normals to grid order, moments and response; 2. suppression over the candidates; 3. the flagged
+  // records listed in ascending original index
+  HIPCK(launch_harris_response(g, nf, d_nrm.p, d_pack.p, r2, threshold, d_rpos.p, response ? d_resp.p : nullptr,
+                               covar ? d_cov.p : nullptr, n_neighbors ? d_cnt.p : nullptr, d_fb.p, d_fbn.p, d_ctr.p, s));
+  if (nonmax) {
+    HIPCK(launch_harris_nms(g, nf, d_rpos.p, r2, threshold, d_flag.p, d_fb.p, d_fbn.p, d_ctr.p, s));
+    HIPCK(launch_harris_compact(d_flag.p, d_pos.p, n, d_scratch.p, sb, d_list.p, s));
+  }
+  if ((rc = sync(ctx))) return rc;
+  const double t2 = now_ms();
+  unsigned long long slots[3 * kHarCtrSlots], ctr[3] = {0, 0, 0};
+  uint32_t nkp = 0;
+  if (nonmax) {
+    HIPCK(hipMemcpyAsync(keypoints, d_list.p, n * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCK(hipMemcpyAsync(&nkp, d_pos.p + n, sizeof(nkp), hipMemcpyDeviceToHost, s));
+  }
+  if (response) HIPCK(hipMemcpyAsync(response, d_resp.p, n * sizeof(float), hipMemcpyDeviceToHost, s));
+  if (covar) HIPCK(hipMemcpyAsync(covar, d_cov.p, 6 * n * sizeof(float), hipMemcpyDeviceToHost, s));
+  if (n_neighbors) HIPCK(hipMemcpyAsync(n_neighbors, d_cnt.p, n * sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCK(hipMemcpyAsync(slots, d_ctr.p, sizeof(slots), hipMemcpyDeviceToHost, s));
+  if ((rc = sync(ctx))) return rc;
+  for (int i = 0; i < 3 * kHarCtrSlots; ++i) ctr[i % 3] += slots[i];
+  if (!nonmax) {  // PCL's branch: the whole response cloud, every record
+    for (size_t i = 0; i < n; ++i) keypoints[i] = static_cast<int>(i);
+    nkp = static_cast<uint32_t>(n);
+  }
+  *n_keypoints = nkp;
+  inf.n_finite = static_cast<double>(nf);
+  inf.n_candidates = static_cast<double>(ctr[1]);
+  inf.n_keypoints = static_cast<double>(nkp);
+  inf.n_tied = static_cast<double>(ctr[2]);
+  inf.pair_tests = static_cast<double>(ctr[0]);
   inf.ms_grid = t1 - t0;
   inf.ms_device = t2 - t1;
   inf.ms_total = now_ms() - t0;

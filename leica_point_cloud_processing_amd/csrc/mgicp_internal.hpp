@@ -385,6 +385,25 @@ hipError_t launch_fpfh_final(const GridView& g, const int* kp, size_t nk, const 
                              const uint16_t* rows, const int* msize, const unsigned int* too_big, float* out,
                              unsigned long long* ctr, hipStream_t s);
 
+// HarrisKeypoint3D with a radius search (InitialAlignment::obtainHarrisKeypoints) over a grid of n finite
+// points.  response: the normals (3 floats per original record) packed into nrm (n, grid order); for every
+// grid point, over its set "float d2 < r2", the normal moments and the Harris response, into resp_pos (by
+// sorted position) and, each nullable and preset by the caller for records outside the grid, resp_orig,
+// covar (6 floats) and count by original index.  nms: flag[original index] = 1 (flag zeroed by the caller)
+// for every point with a finite response not below thr that no member of its set exceeds.  compact: the
+// flagged original indices, ascending, into list; their number lands in pos[records] (flag / pos:
+// records + 1 words, flag[records] = 0).  fb / fb_count (n entries / one counter): the records a lane hands
+// to the wave-per-record launch.  ctr (3 * kHarCtrSlots words, zeroed by the caller): triples of
+// {distance evaluations, candidates, tied keypoints}; the totals are the sums over the slots.
+constexpr int kHarCtrSlots = 256;
+hipError_t launch_harris_response(const GridView& g, size_t n, const float* normals, float4* nrm, float r2, float thr,
+                                  float* resp_pos, float* resp_orig, float* covar, int* count, uint32_t* fb,
+                                  unsigned int* fb_count, unsigned long long* ctr, hipStream_t s);
+hipError_t launch_harris_nms(const GridView& g, size_t n, const float* resp_pos, float r2, float thr, uint32_t* flag,
+                             uint32_t* fb, unsigned int* fb_count, unsigned long long* ctr, hipStream_t s);
+hipError_t launch_harris_compact(const uint32_t* flag, uint32_t* pos, size_t records, void* scratch,
+                                 size_t scratch_bytes, uint32_t* list, hipStream_t s);
+
 // CorrespondenceEstimation over 33-float descriptors (InitialAlignment::obtainCorrespondences): exact brute
 // force.  src / tgt: ns / nt packed rows of 33 finite floats.  A source row's state is the key
 // (d2 bits << 32) | (target row << 1) | tied, kMatchNone before any target with d2 < FLT_MAX; keys order as

@@ -4254,6 +4254,301 @@ __global__ __launch_bounds__(64) void fpfh_final_kernel(GridView g, const int* _
 }
 
 // ------------------------------------------------------------------------------------
+// Harris keypoints (pcl::HarrisKeypoint3D, method HARRIS, with a radius search and non-maximum
+// suppression, as InitialAlignment::obtainHarrisKeypoints calls it) -- DESIGN.md "Harris keypoints".
+// ------------------------------------------------------------------------------------
+// Two sweeps over a grid whose cell edge is one radius, a lane per record in grid order (the reference's
+// radius gives a record 1-8 neighbours: a tile or a wave per record would idle most lanes):
+//   harris_pack_kernel      the normals into grid order, 16 bytes each, so a sweep reads them by position
+//   harris_response_kernel  |N|, c, the six fp64 sums of the float products, covar and the response
+//   harris_nms_kernel       candidates only (finite response, not below the threshold): a lane leaves at the
+//                           first larger neighbour; a wave without candidates leaves at once, and a wave's
+//                           walk ends with its last lane (the loop is per lane, so the exec mask is the
+//                           ballot)
+// A lane takes its cell box -- har_box, the box of normals_tile_kernel for a single query, exact for any
+// cell edge by the same argument -- row by row, (z, y) ascending and positions ascending within a row: a
+// fixed order, so the fp64 sums have the same bits on every call.  A record whose box holds more than
+// kHarLaneCap candidates (known before a row is walked: the box's rows are added up as they come) is
+// listed instead and taken by a wave in the hand-off launch (harris_*_wave_kernel): row by row again,
+// lane l taking the row's positions l, l + 64, ..., the lanes' sums then through wave_sum's tree --
+// another fixed order, and the path of a record depends on the cloud and the radius alone.
+// ctr: kHarCtrSlots triples {pair tests, candidates, tied keypoints}, a wave adding to the triple of its
+// index modulo the slots (the FPFH kernels' reason); the host sums the slots.
+constexpr uint32_t kHarLaneCap = 512;  // candidates of a box a lane walks itself
+
+struct HarBox {
+  int xa, xb, ya, yb, za, zb;
+};
+
+__device__ __forceinline__ HarBox har_box(const GridView& g, const float4& q, float r2) {
+  const float rx = sqrtf(r2) * 1.0001f + g.slop;
+  HarBox b;
+  b.xa = bcell(q.x - rx, g.ox, g.inv_h, g.nx);
+  b.xb = bcell(q.x + rx, g.ox, g.inv_h, g.nx);
+  b.ya = bcell(q.y - rx, g.oy, g.inv_h, g.ny);
+  b.yb = bcell(q.y + rx, g.oy, g.inv_h, g.ny);
+  b.za = bcell(q.z - rx, g.oz, g.inv_h, g.nz);
+  b.zb = bcell(q.z + rx, g.oz, g.inv_h, g.nz);
+  return b;
+}
+
+// a neighbour's normal into the count and the sums: PCL counts by normal_x alone
+__device__ __forceinline__ void har_add(const float4& nj, int& c, double (&S)[6]) {
+  if (!isfinite(nj.x)) return;
+  ++c;
+  S[0] += static_cast<double>(nj.x * nj.x);
+  S[1] += static_cast<double>(nj.x * nj.y);
+  S[2] += static_cast<double>(nj.x * nj.z);
+  S[3] += static_cast<double>(nj.y * nj.y);
+  S[4] += static_cast<double>(nj.y * nj.z);
+  S[5] += static_cast<double>(nj.z * nj.z);
+}
+
+// covar = (float)(S / c), PCL's responseHarris on it in float, left to right; the outputs of one record
+__device__ __forceinline__ bool har_finish(int m, int c, const double (&S)[6], uint32_t p, uint32_t oi, float thr,
+                                           float* __restrict__ resp_pos, float* __restrict__ resp_orig,
+                                           float* __restrict__ covar_orig, int* __restrict__ count_orig) {
+  float v[6];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) v[k] = c > 0 ? static_cast<float>(S[k] / static_cast<double>(c)) : 0.f;
+  const float xx = v[0], xy = v[1], xz = v[2], yy = v[3], yz = v[4], zz = v[5];
+  const float trace = (xx + yy) + zz;
+  float r = 0.f;
+  if (trace != 0.f) {
+    float det = (xx * yy) * zz;
+    det = det + ((2.f * xy) * xz) * yz;
+    det = det - (xz * xz) * yy;
+    det = det - (xy * xy) * zz;
+    det = det - (yz * yz) * xx;
+    r = (0.04f + det) - (0.04f * trace) * trace;
+  }
+  resp_pos[p] = r;
+  if (resp_orig) resp_orig[oi] = r;
+  if (count_orig) count_orig[oi] = m;
+  if (covar_orig) {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) covar_orig[static_cast<size_t>(oi) * 6 + k] = v[k];
+  }
+  return isfinite(r) && !(r < thr);
+}
+
+__device__ __forceinline__ void har_count(unsigned long long* __restrict__ ctr, size_t wave, int lane,
+                                          unsigned long long tests, bool cand, bool tied) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) tests += __shfl_down(tests, off, 64);
+  const unsigned long long nc = __popcll(__ballot(cand)), nt = __popcll(__ballot(tied));
+  if (lane == 0) {
+    unsigned long long* slot = ctr + 3 * (wave % kHarCtrSlots);
+    if (tests) atomicAdd(slot, tests);
+    if (nc) atomicAdd(slot + 1, nc);
+    if (nt) atomicAdd(slot + 2, nt);
+  }
+}
+
+__global__ void harris_pack_kernel(const float4* __restrict__ pts, size_t n, const float* __restrict__ normals,
+                                   float4* __restrict__ nrm) {
+  const size_t p = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (p >= n) return;
+  const size_t oi = __float_as_uint(pts[p].w);
+  nrm[p] = make_float4(normals[3 * oi], normals[3 * oi + 1], normals[3 * oi + 2], 0.f);
+}
+
+__global__ __launch_bounds__(256) void harris_response_kernel(GridView g, size_t n, const float4* __restrict__ nrm,
+                                                              float r2, float thr, float* __restrict__ resp_pos,
+                                                              float* __restrict__ resp_orig,
+                                                              float* __restrict__ covar_orig,
+                                                              int* __restrict__ count_orig, uint32_t* __restrict__ fb,
+                                                              unsigned int* __restrict__ fb_count,
+                                                              unsigned long long* __restrict__ ctr) {
+  const size_t p = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  unsigned long long tests = 0;
+  bool cand = false;
+  if (p < n) {
+    const float4 q = g.pts[p];
+    const HarBox b = har_box(g, q, r2);
+    int m = 0, c = 0;
+    double S[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    uint32_t seen = 0;
+    bool mine = true;
+    for (int z = b.za; z <= b.zb && mine; ++z) {
+      for (int y = b.ya; y <= b.yb; ++y) {
+        const uint32_t* row = g.cell_start + (static_cast<size_t>(z) * g.ny + y) * g.nx;
+        const uint32_t ja = row[b.xa], jb = row[b.xb + 1];
+        seen += jb - ja;
+        if (seen > kHarLaneCap) {
+          mine = false;
+          break;
+        }
+        for (uint32_t j = ja; j < jb; ++j)
+          if (dist2(q.x, q.y, q.z, g.pts[j]) < r2) {
+            ++m;
+            har_add(nrm[j], c, S);
+          }
+        tests += jb - ja;
+      }
+    }
+    if (mine)
+      cand = har_finish(m, c, S, static_cast<uint32_t>(p), __float_as_uint(q.w), thr, resp_pos, resp_orig, covar_orig,
+                        count_orig);
+    else
+      fb[atomicAdd(fb_count, 1u)] = static_cast<uint32_t>(p);
+  }
+  har_count(ctr, (static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x) >> 6, threadIdx.x & 63, tests, cand,
+            false);
+}
+
+// the box of a listed record, a row of cells at a time: f(j) for lane l at the row's positions l, l + 64, ...;
+// stop() (one answer per wave) ends the walk after a row
+template <class F, class Stop>
+__device__ __forceinline__ unsigned long long har_wave_rows(const GridView& g, const float4& q, float r2, int lane,
+                                                            F&& f, Stop&& stop) {
+  const HarBox b = har_box(g, q, r2);  // q is the wave's: every lane holds the same box
+  unsigned long long tests = 0;
+  for (int z = b.za; z <= b.zb; ++z) {
+    for (int y = b.ya; y <= b.yb; ++y) {
+      const uint32_t* row = g.cell_start + (static_cast<size_t>(z) * g.ny + y) * g.nx;
+      const uint32_t ja = row[b.xa], jb = row[b.xb + 1];
+      for (uint32_t j = ja + static_cast<uint32_t>(lane); j < jb; j += 64) f(j);
+      tests += jb - ja;
+      if (stop()) return tests;
+    }
+  }
+  return tests;
+}
+
+__global__ __launch_bounds__(64) void harris_response_wave_kernel(GridView g, const uint32_t* __restrict__ list,
+                                                                  const unsigned int* __restrict__ count,
+                                                                  const float4* __restrict__ nrm, float r2, float thr,
+                                                                  float* __restrict__ resp_pos,
+                                                                  float* __restrict__ resp_orig,
+                                                                  float* __restrict__ covar_orig,
+                                                                  int* __restrict__ count_orig,
+                                                                  unsigned long long* __restrict__ ctr) {
+  const int lane = threadIdx.x;
+  const uint32_t nl = *count;
+  unsigned long long tests = 0;
+  int ncand = 0;
+  for (uint32_t idx = blockIdx.x; idx < nl; idx += gridDim.x) {
+    const uint32_t p = list[idx];
+    const float4 q = g.pts[p];
+    int m = 0, c = 0;
+    double S[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    tests += har_wave_rows(
+        g, q, r2, lane,
+        [&](uint32_t j) {
+          if (dist2(q.x, q.y, q.z, g.pts[j]) < r2) {
+            ++m;
+            har_add(nrm[j], c, S);
+          }
+        },
+        [] { return false; });
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      m += __shfl_down(m, off, 64);
+      c += __shfl_down(c, off, 64);
+    }
+#pragma unroll
+    for (int k = 0; k < 6; ++k) S[k] = wave_sum(S[k]);
+    if (lane == 0)
+      ncand += har_finish(m, c, S, p, __float_as_uint(q.w), thr, resp_pos, resp_orig, covar_orig, count_orig) ? 1 : 0;
+  }
+  if (lane == 0) {
+    unsigned long long* slot = ctr + 3 * (blockIdx.x % kHarCtrSlots);
+    if (tests) atomicAdd(slot, tests);
+    if (ncand) atomicAdd(slot + 1, static_cast<unsigned long long>(ncand));
+  }
+}
+
+// a candidate is a keypoint unless a member of its set has a larger response (a NaN compares false both
+// ways: it suppresses nothing); tied: another member has the same response.  flag: one word per original
+// record, zeroed by the caller
+__global__ __launch_bounds__(256) void harris_nms_kernel(GridView g, size_t n, const float* __restrict__ resp_pos,
+                                                         float r2, float thr, uint32_t* __restrict__ flag_orig,
+                                                         uint32_t* __restrict__ fb, unsigned int* __restrict__ fb_count,
+                                                         unsigned long long* __restrict__ ctr) {
+  const size_t p = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  const float my = p < n ? resp_pos[p] : __uint_as_float(0x7fc00000u);
+  const bool cand = isfinite(my) && !(my < thr);
+  if (!__ballot(cand)) return;  // the wave
+  unsigned long long tests = 0;
+  bool tied = false;
+  if (cand) {
+    const float4 q = g.pts[p];
+    const HarBox b = har_box(g, q, r2);
+    uint32_t seen = 0;
+    bool mine = true, top = true;
+    for (int z = b.za; z <= b.zb && mine && top; ++z) {
+      for (int y = b.ya; y <= b.yb && top; ++y) {
+        const uint32_t* row = g.cell_start + (static_cast<size_t>(z) * g.ny + y) * g.nx;
+        const uint32_t ja = row[b.xa], jb = row[b.xb + 1];
+        seen += jb - ja;
+        if (seen > kHarLaneCap) {
+          mine = false;
+          break;
+        }
+        uint32_t j = ja;
+        for (; j < jb; ++j) {
+          if (!(dist2(q.x, q.y, q.z, g.pts[j]) < r2)) continue;
+          const float rj = resp_pos[j];
+          if (my < rj) {
+            top = false;
+            ++j;
+            break;
+          }
+          tied = tied || (rj == my && j != static_cast<uint32_t>(p));
+        }
+        tests += j - ja;
+      }
+    }
+    if (!mine)
+      fb[atomicAdd(fb_count, 1u)] = static_cast<uint32_t>(p);
+    else if (top)
+      flag_orig[__float_as_uint(q.w)] = 1u;
+    tied = tied && mine && top;
+  }
+  har_count(ctr, (static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x) >> 6, threadIdx.x & 63, tests, false,
+            tied);
+}
+
+__global__ __launch_bounds__(64) void harris_nms_wave_kernel(GridView g, const uint32_t* __restrict__ list,
+                                                             const unsigned int* __restrict__ count,
+                                                             const float* __restrict__ resp_pos, float r2,
+                                                             uint32_t* __restrict__ flag_orig,
+                                                             unsigned long long* __restrict__ ctr) {
+  const int lane = threadIdx.x;
+  const uint32_t nl = *count;
+  unsigned long long tests = 0;
+  int ntied = 0;
+  for (uint32_t idx = blockIdx.x; idx < nl; idx += gridDim.x) {
+    const uint32_t p = list[idx];
+    const float4 q = g.pts[p];
+    const float my = resp_pos[p];
+    bool larger = false, tied = false;
+    tests += har_wave_rows(
+        g, q, r2, lane,
+        [&](uint32_t j) {
+          if (dist2(q.x, q.y, q.z, g.pts[j]) < r2) {
+            const float rj = resp_pos[j];
+            larger = larger || my < rj;
+            tied = tied || (rj == my && j != p);
+          }
+        },
+        [&] { return __ballot(larger) != 0ull; });
+    const bool top = !__ballot(larger);
+    const bool any_tied = __ballot(tied) != 0ull;
+    if (lane == 0 && top) {
+      flag_orig[__float_as_uint(q.w)] = 1u;
+      ntied += any_tied ? 1 : 0;
+    }
+  }
+  if (lane == 0) {
+    unsigned long long* slot = ctr + 3 * (blockIdx.x % kHarCtrSlots);
+    if (tests) atomicAdd(slot, tests);
+    if (ntied) atomicAdd(slot + 2, static_cast<unsigned long long>(ntied));
+  }
+}
+
+// ------------------------------------------------------------------------------------
 // Feature correspondences (pcl::registration::CorrespondenceEstimation over FPFHSignature33, as
 // InitialAlignment::obtainCorrespondences calls it) -- DESIGN.md "Feature correspondences".
 // Exact brute force over packed rows of 33 floats, the non-finite rows already dropped by the host.
@@ -5132,6 +5427,40 @@ hipError_t launch_fpfh_final(const GridView& g, const int* kp, size_t nk, const 
   return hipGetLastError();
 }
 
+hipError_t launch_harris_response(const GridView& g, size_t n, const float* normals, float4* nrm, float r2, float thr,
+                                  float* resp_pos, float* resp_orig, float* covar, int* count, uint32_t* fb,
+                                  unsigned int* fb_count, unsigned long long* ctr, hipStream_t s) {
+  if (!n) return hipSuccess;
+  hipError_t e = hipMemsetAsync(fb_count, 0, sizeof(unsigned int), s);
+  if (e != hipSuccess) return e;
+  harris_pack_kernel<<<nblk(n), 256, 0, s>>>(g.pts, n, normals, nrm);
+  harris_response_kernel<<<nblk(n), 256, 0, s>>>(g, n, nrm, r2, thr, resp_pos, resp_orig, covar, count, fb, fb_count, ctr);
+  // the hand-off follows in stream order, its count read on the device; blocks past the list end at once
+  harris_response_wave_kernel<<<static_cast<unsigned>(std::min<size_t>(n, 4096)), 64, 0, s>>>(
+      g, fb, fb_count, nrm, r2, thr, resp_pos, resp_orig, covar, count, ctr);
+  return hipGetLastError();
+}
+
+hipError_t launch_harris_nms(const GridView& g, size_t n, const float* resp_pos, float r2, float thr, uint32_t* flag,
+                             uint32_t* fb, unsigned int* fb_count, unsigned long long* ctr, hipStream_t s) {
+  if (!n) return hipSuccess;
+  hipError_t e = hipMemsetAsync(fb_count, 0, sizeof(unsigned int), s);
+  if (e != hipSuccess) return e;
+  harris_nms_kernel<<<nblk(n), 256, 0, s>>>(g, n, resp_pos, r2, thr, flag, fb, fb_count, ctr);
+  harris_nms_wave_kernel<<<static_cast<unsigned>(std::min<size_t>(n, 4096)), 64, 0, s>>>(g, fb, fb_count, resp_pos, r2,
+                                                                                       flag, ctr);
+  return hipGetLastError();
+}
+
+hipError_t launch_harris_compact(const uint32_t* flag, uint32_t* pos, size_t records, void* scratch,
+                                 size_t scratch_bytes, uint32_t* list, hipStream_t s) {
+  if (!records) return hipSuccess;
+  hipError_t e = launch_exclusive_scan(scratch, scratch_bytes, flag, pos, records + 1, s);
+  if (e != hipSuccess) return e;
+  fpfh_list_kernel<<<nblk(records), 256, 0, s>>>(flag, pos, records, list);
+  return hipGetLastError();
+}
+
 MatchLayout match_layout(size_t ns, size_t count) {
   const size_t bx = (ns + kMatchBlock - 1) / kMatchBlock;
   // few source blocks: the targets of the launch are shared out until about kMatchBlocksWanted blocks run
@@ -5574,6 +5903,11 @@ hipError_t preload_kernels(void* pinned, size_t pinned_bytes, hipStream_t s) {
       reinterpret_cast<const void*>(&fpfh_list_kernel),
       reinterpret_cast<const void*>(&fpfh_spfh_kernel),
       reinterpret_cast<const void*>(&fpfh_final_kernel),
+      reinterpret_cast<const void*>(&harris_pack_kernel),
+      reinterpret_cast<const void*>(&harris_response_kernel),
+      reinterpret_cast<const void*>(&harris_response_wave_kernel),
+      reinterpret_cast<const void*>(&harris_nms_kernel),
+      reinterpret_cast<const void*>(&harris_nms_wave_kernel),
       reinterpret_cast<const void*>(&match_kernel),
       reinterpret_cast<const void*>(&match_merge_kernel),
   };

@@ -308,6 +308,32 @@ class GICPEngine:
         info = {f: getattr(bi, f) for f, _ in bi._fields_}
         return (flags[:n].astype(bool), gap[:n] if want_gap else None, nn[:n] if want_indices else None, info)
 
+    def harris_keypoints(self, cloud, normals, radius: float, threshold: float = 1e-6, nonmax: bool = True,
+                         want_response: bool = False, want_covar: bool = False, want_counts: bool = False):
+        """pcl::HarrisKeypoint3D (method HARRIS) with a radius search (InitialAlignment::obtainHarrisKeypoints):
+        (keypoints int32[nk] ascending, response float32[n] | None, covar float32[n, 6] | None, n_neighbors
+        int32[n] | None, info).  `normals` is float32 [n, 3] or [n, 4], one per record of `cloud`.  A keypoint
+        is a finite record with a finite response not below float32(threshold) that no record within the
+        radius exceeds; nonmax False lists every record, as PCL's branch does."""
+        _keep, ptr, n, stride = self._cloud_arg(cloud)
+        nrm = np.ascontiguousarray(normals, dtype=np.float32)
+        if nrm.ndim != 2 or nrm.shape[1] < 3 or len(nrm) != n:
+            raise ValueError(f"normals must be [{n}, 3] or [{n}, 4], got {nrm.shape}")
+        kp = np.full(max(n, 1), -1, np.int32)
+        resp = np.zeros(max(n, 1), np.float32) if want_response else None
+        cov = np.zeros((max(n, 1), 6), np.float32) if want_covar else None
+        cnt = np.zeros(max(n, 1), np.int32) if want_counts else None
+        nk = ctypes.c_size_t()
+        hi = _lib.MgicpHarrisInfo()
+        self._check(self._lib.mgicp_harris_keypoints(
+            self._h, ctypes.c_void_p(ptr), n, stride, ctypes.c_void_p(nrm.ctypes.data), 4 * nrm.shape[1],
+            float(radius), float(np.float32(threshold)), 1 if nonmax else 0, kp.ctypes.data, ctypes.byref(nk),
+            resp.ctypes.data if want_response else None, cov.ctypes.data if want_covar else None,
+            cnt.ctypes.data if want_counts else None, ctypes.byref(hi)), "harris_keypoints")
+        info = {f: getattr(hi, f) for f, _ in hi._fields_}
+        return (kp[:nk.value].copy(), resp[:n] if want_response else None, cov[:n] if want_covar else None,
+                cnt[:n] if want_counts else None, info)
+
     def fpfh_features(self, cloud, normals, keypoints=None, radius: float = 0.0, want_spfh: bool = False):
         """pcl::FPFHEstimation with a radius search (InitialAlignment::obtainFeatures): (fpfh float32
         [nk, 33], spfh_counts uint16[n, 33] | None, spfh_sizes int32[n] | None, info).  `normals` is float32

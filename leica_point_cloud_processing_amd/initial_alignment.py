@@ -1,10 +1,12 @@
 """InitialAlignment -- the pre-alignment's steps that run on the MI355X engine.
 
-Three members of the reference class (src/InitialAlignment.cpp): obtainBoundaryKeypoints, the keypoint step
-of the BOUNDARY (default) and NORMALS methods, obtainFeatures, the FPFH descriptors at the keypoints
-(BOUNDARY and HARRIS), and obtainCorrespondences, the nearest target descriptor of every source descriptor.
-The normals they take come from gicp_alignment.getNormals (Utils::getNormals).  Only the rejectors
-(rejectCorrespondences, rejectOneToOneCorrespondences) and estimateTransform remain off the engine.
+Four members of the reference class (src/InitialAlignment.cpp): obtainBoundaryKeypoints, the keypoint step
+of the BOUNDARY (default) and NORMALS methods, obtainHarrisKeypoints, the keypoint step of HARRIS,
+obtainFeatures, the FPFH descriptors at the keypoints (BOUNDARY and HARRIS), and obtainCorrespondences, the
+nearest target descriptor of every source descriptor.  BOUNDARY and HARRIS thus run on the engine from the
+normals to the correspondences.  The normals they take come from gicp_alignment.getNormals
+(Utils::getNormals).  Only the rejectors (rejectCorrespondences, rejectOneToOneCorrespondences) and
+estimateTransform remain off the engine.
 """
 from __future__ import annotations
 
@@ -16,6 +18,7 @@ from .engine import GICPEngine
 BOUNDARY_K_SEARCH = 30             # detector.setKSearch(30)
 BOUNDARY_ANGLE_THRESHOLD = 1.047   # detector.setAngleThreshold(1.047f)
 RADIUS_FACTOR = 1.4                # radius_factor_ (the constructor's default)
+HARRIS_THRESHOLD = np.float32(1e-6)  # detector.setThreshold(1e-6): PCL's threshold_ is a float
 
 
 def obtainBoundaryKeypoints(cloud, normals, engine: GICPEngine | None = None):
@@ -38,6 +41,26 @@ def obtainBoundaryKeypoints(cloud, normals, engine: GICPEngine | None = None):
     keypoints = np.flatnonzero(boundary).astype(np.int32)
     non_keypoints = np.flatnonzero(~boundary).astype(np.int32)
     return (-1 if len(keypoints) == 0 else 0), keypoints, non_keypoints
+
+
+def obtainHarrisKeypoints(cloud, normals, radius_factor: float = RADIUS_FACTOR, engine: GICPEngine | None = None):
+    """InitialAlignment::obtainHarrisKeypoints (src/InitialAlignment.cpp:399-424): pcl::HarrisKeypoint3D with
+    non-maximum suppression, a threshold of float32(1e-6) and a radius of
+    float32(computeCloudResolution(cloud) * radius_factor) (PCL's setRadius takes a float).  `normals` is
+    float32 [n, 3] or [n, 4] (getNormals' array).  Returns (status, keypoints_indices), the indices an
+    ascending int32 array: status -1 when len(normals) != len(cloud) or when no keypoint is found, else 0.
+    The keypoint cloud is cloud[keypoints_indices]."""
+    size = cloud.size() if isinstance(cloud, PointCloudRGB) else len(np.asarray(cloud).reshape(-1, 3))
+    normals = np.asarray(normals, dtype=np.float32)
+    if normals.ndim != 2 or len(normals) != size:
+        return -1, np.zeros(0, np.int32)
+    if engine is None:
+        from .filter import _engine
+
+        engine = _engine()
+    radius = float(np.float32(engine.cloud_resolution(cloud) * radius_factor))
+    keypoints, _resp, _cov, _cnt, _info = engine.harris_keypoints(cloud, normals, radius, HARRIS_THRESHOLD, True)
+    return (-1 if len(keypoints) == 0 else 0), keypoints
 
 
 def obtainFeatures(cloud, normals, keypoints_indices, radius_factor: float = RADIUS_FACTOR,
