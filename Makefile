@@ -4,7 +4,8 @@ ARCH  ?= gfx950
 PKG   := leica_point_cloud_processing_amd
 LIB   := $(PKG)/libmgicp.so
 SRCS  := $(PKG)/csrc/mgicp_kernels.hip $(PKG)/csrc/mgicp_engine.hip $(PKG)/csrc/mgicp_clouds.hip \
-         $(PKG)/csrc/mgicp_pass.hip $(PKG)/csrc/mgicp_fod.hip $(PKG)/csrc/mgicp_comm.hip $(PKG)/csrc/mgicp_debug.hip
+         $(PKG)/csrc/mgicp_pass.hip $(PKG)/csrc/mgicp_fod.hip $(PKG)/csrc/mgicp_features.hip $(PKG)/csrc/mgicp_comm.hip \
+         $(PKG)/csrc/mgicp_debug.hip
 HDRS  := $(wildcard $(PKG)/csrc/*.hpp) include/mi355x_gicp.h include/mi355x_gicp_debug.h
 # the export map: the library's dynamic symbols are the mgicp_* functions of the two headers, all else local
 MAP   := $(PKG)/csrc/libmgicp.map
@@ -13,11 +14,11 @@ LDMAP := -Wl,--version-script=$(MAP)
 HIPFLAGS := -O3 -std=c++17 --offload-arch=$(ARCH) -fPIC -ffp-contract=off -Wall -Wno-unused-result
 
 all: $(LIB) oracle adapter-example adapter-replay fod-replay normals-replay boundary-replay fpfh-replay corr-replay \
-     harris-replay
+     harris-replay ia-replay
 
 OBJDIR := $(PKG)/csrc/build
 OBJS  := $(OBJDIR)/mgicp_kernels.o $(OBJDIR)/mgicp_engine.o $(OBJDIR)/mgicp_clouds.o $(OBJDIR)/mgicp_pass.o \
-         $(OBJDIR)/mgicp_fod.o $(OBJDIR)/mgicp_comm.o $(OBJDIR)/mgicp_debug.o
+         $(OBJDIR)/mgicp_fod.o $(OBJDIR)/mgicp_features.o $(OBJDIR)/mgicp_comm.o $(OBJDIR)/mgicp_debug.o
 
 # one object per source (make -j compiles them side by side; an engine edit does not rebuild the kernels)
 $(OBJDIR)/%.o: $(PKG)/csrc/%.hip $(HDRS)
@@ -37,114 +38,46 @@ adapter/cabi_example: adapter/cabi_example.cpp include/mi355x_gicp.h $(LIB)
 
 adapter-example: adapter/cabi_example
 
-# the drop-in adapter itself (adapter/GICPAlignment.cpp + adapter/Filter_mi355x.cpp), compiled as the
-# catkin package would compile it (-std=c++14, the reference's CMakeLists.txt:6) against the
-# layout-exact PCL / Eigen / ROS stand-ins of tests/adapter_standins (PCL and ROS are absent here),
-# linked with a replay of test/test_gicp_alignment.cpp:50-131 (test infrastructure)
-STANDIN := tests/adapter_standins
-REPLAY  := adapter/build/replay_test_gicp_alignment
-$(REPLAY): adapter/GICPAlignment.cpp adapter/GICPAlignment.h adapter/Filter_mi355x.cpp include/mi355x_gicp.h \
-           $(wildcard $(STANDIN)/*.h) $(STANDIN)/Utils_standin.cpp $(STANDIN)/replay_test_gicp_alignment.cpp $(LIB)
-	mkdir -p adapter/build
-	g++ -O2 -std=c++14 -Wall -Wextra -Werror -I$(STANDIN) -Iadapter -Iinclude -o $@ \
-	    adapter/GICPAlignment.cpp adapter/Filter_mi355x.cpp $(STANDIN)/Utils_standin.cpp \
-	    $(STANDIN)/replay_test_gicp_alignment.cpp -L$(PKG) -lmgicp -Wl,-rpath,'$$ORIGIN/../../$(PKG)'
-
-adapter-replay: $(REPLAY)
-
-# adapter/FODDetector_mi355x.cpp (FODDetector::clusterPossibleFODs) compiled the same way, against the
-# stand-ins above plus those of tests/adapter_standins_fod (FODDetector.h, pcl::PointIndices, the members
-# the adapter leaves alone), linked with a replay of test/test_fod_detector.cpp's testFODClustering and
-# testEmptyCloud (test infrastructure)
+# The adapter files, each compiled as the catkin package would compile it (-std=c++14, the reference's
+# CMakeLists.txt:6) against layout-exact PCL / Eigen / ROS stand-ins (PCL and ROS are absent here) and
+# linked with a replay driver (test infrastructure).  tests/adapter_standins holds the common stand-ins;
+# a directory in front of it on the include path adds or replaces the headers of one adapter file.
+#   $(call replay_rule,<target>,<binary under adapter/build>,<adapter sources>,
+#          <stand-in directories, the first in front>,<stand-in sources and the driver>)
+STANDIN     := tests/adapter_standins
 STANDIN_FOD := tests/adapter_standins_fod
-FODREPLAY   := adapter/build/replay_test_fod_detector
-$(FODREPLAY): adapter/FODDetector_mi355x.cpp include/mi355x_gicp.h $(wildcard $(STANDIN)/*.h) \
-              $(wildcard $(STANDIN_FOD)/*.h) $(STANDIN)/Utils_standin.cpp $(STANDIN_FOD)/FODDetector_standin.cpp \
-              $(STANDIN_FOD)/replay_test_fod_detector.cpp $(LIB)
-	mkdir -p adapter/build
-	g++ -O2 -std=c++14 -Wall -Wextra -Werror -I$(STANDIN_FOD) -I$(STANDIN) -Iadapter -Iinclude -o $@ \
-	    adapter/FODDetector_mi355x.cpp $(STANDIN)/Utils_standin.cpp $(STANDIN_FOD)/FODDetector_standin.cpp \
-	    $(STANDIN_FOD)/replay_test_fod_detector.cpp -L$(PKG) -lmgicp -Wl,-rpath,'$$ORIGIN/../../$(PKG)'
-
-fod-replay: $(FODREPLAY)
-
-# adapter/Utils_mi355x.cpp (Utils::getNormals) compiled the same way, against the stand-ins above with the
-# Utils.h of tests/adapter_standins_normals in front (getNormals and a layout-exact pcl::Normal), linked
-# with a driver that runs it as InitialAlignment's constructor does (test infrastructure)
 STANDIN_NRM := tests/adapter_standins_normals
-NRMREPLAY   := adapter/build/replay_test_normals
-$(NRMREPLAY): adapter/Utils_mi355x.cpp include/mi355x_gicp.h $(wildcard $(STANDIN)/*.h) \
-              $(wildcard $(STANDIN_NRM)/*.h) $(STANDIN)/Utils_standin.cpp $(STANDIN_NRM)/replay_test_normals.cpp $(LIB)
+STANDIN_IA  := tests/adapter_standins_ia
+define replay_rule
+adapter/build/$(2): $(3) $$(wildcard adapter/*.h) include/mi355x_gicp.h $$(foreach d,$(4),$$(wildcard $$(d)/*.h)) $(5) $$(LIB)
 	mkdir -p adapter/build
-	g++ -O2 -std=c++14 -Wall -Wextra -Werror -I$(STANDIN_NRM) -I$(STANDIN) -Iadapter -Iinclude -o $@ \
-	    adapter/Utils_mi355x.cpp $(STANDIN)/Utils_standin.cpp $(STANDIN_NRM)/replay_test_normals.cpp \
-	    -L$(PKG) -lmgicp -Wl,-rpath,'$$ORIGIN/../../$(PKG)'
+	g++ -O2 -std=c++14 -Wall -Wextra -Werror $$(addprefix -I,$(4)) -Iadapter -Iinclude -o $$@ \
+	    $(3) $(5) -L$$(PKG) -lmgicp -Wl,-rpath,'$$$$ORIGIN/../../$$(PKG)'
 
-normals-replay: $(NRMREPLAY)
+$(1): adapter/build/$(2)
+endef
 
-# adapter/InitialAlignment_mi355x.cpp (InitialAlignment::obtainBoundaryKeypoints) compiled the same way: the
-# InitialAlignment.h of tests/adapter_standins_boundary in front (the class with that private member), then
-# the Utils.h with pcl::Normal, linked with a driver that calls it on a cloud file and a normals file
-# (test infrastructure)
-STANDIN_BND := tests/adapter_standins_boundary
-BNDREPLAY   := adapter/build/replay_test_boundary
-$(BNDREPLAY): adapter/InitialAlignment_mi355x.cpp include/mi355x_gicp.h $(wildcard $(STANDIN)/*.h) \
-              $(wildcard $(STANDIN_NRM)/*.h) $(wildcard $(STANDIN_BND)/*.h) $(STANDIN)/Utils_standin.cpp \
-              $(STANDIN_BND)/replay_test_boundary.cpp $(LIB)
-	mkdir -p adapter/build
-	g++ -O2 -std=c++14 -Wall -Wextra -Werror -I$(STANDIN_BND) -I$(STANDIN_NRM) -I$(STANDIN) -Iadapter -Iinclude -o $@ \
-	    adapter/InitialAlignment_mi355x.cpp $(STANDIN)/Utils_standin.cpp $(STANDIN_BND)/replay_test_boundary.cpp \
-	    -L$(PKG) -lmgicp -Wl,-rpath,'$$ORIGIN/../../$(PKG)'
-
-boundary-replay: $(BNDREPLAY)
-
-# adapter/InitialAlignment_features_mi355x.cpp (InitialAlignment::obtainFeatures) compiled the same way: the
-# InitialAlignment.h of tests/adapter_standins_fpfh in front (the class with that private member, its
-# radius_factor_ and pcl::FPFHSignature33), linked with a driver that calls it on a cloud file, a normals
-# file and a keypoint index file (test infrastructure)
-STANDIN_FPFH := tests/adapter_standins_fpfh
-FPFHREPLAY   := adapter/build/replay_test_fpfh
-$(FPFHREPLAY): adapter/InitialAlignment_features_mi355x.cpp include/mi355x_gicp.h $(wildcard $(STANDIN)/*.h) \
-               $(wildcard $(STANDIN_NRM)/*.h) $(wildcard $(STANDIN_FPFH)/*.h) $(STANDIN)/Utils_standin.cpp \
-               $(STANDIN_FPFH)/replay_test_fpfh.cpp $(LIB)
-	mkdir -p adapter/build
-	g++ -O2 -std=c++14 -Wall -Wextra -Werror -I$(STANDIN_FPFH) -I$(STANDIN_NRM) -I$(STANDIN) -Iadapter -Iinclude -o $@ \
-	    adapter/InitialAlignment_features_mi355x.cpp $(STANDIN)/Utils_standin.cpp $(STANDIN_FPFH)/replay_test_fpfh.cpp \
-	    -L$(PKG) -lmgicp -Wl,-rpath,'$$ORIGIN/../../$(PKG)'
-
-fpfh-replay: $(FPFHREPLAY)
-
-# adapter/InitialAlignment_correspondences_mi355x.cpp (InitialAlignment::obtainCorrespondences) compiled the
-# same way: the InitialAlignment.h of tests/adapter_standins_corr in front (the class with that private
-# member, its feature clouds and a pcl::Correspondence with PCL's virtual destructor), linked with a driver
-# that calls it on two feature files (test infrastructure)
-STANDIN_CORR := tests/adapter_standins_corr
-CORRREPLAY   := adapter/build/replay_test_correspondences
-$(CORRREPLAY): adapter/InitialAlignment_correspondences_mi355x.cpp include/mi355x_gicp.h $(wildcard $(STANDIN)/*.h) \
-               $(wildcard $(STANDIN_NRM)/*.h) $(wildcard $(STANDIN_CORR)/*.h) $(STANDIN)/Utils_standin.cpp \
-               $(STANDIN_CORR)/replay_test_correspondences.cpp $(LIB)
-	mkdir -p adapter/build
-	g++ -O2 -std=c++14 -Wall -Wextra -Werror -I$(STANDIN_CORR) -I$(STANDIN_NRM) -I$(STANDIN) -Iadapter -Iinclude -o $@ \
-	    adapter/InitialAlignment_correspondences_mi355x.cpp $(STANDIN)/Utils_standin.cpp \
-	    $(STANDIN_CORR)/replay_test_correspondences.cpp -L$(PKG) -lmgicp -Wl,-rpath,'$$ORIGIN/../../$(PKG)'
-
-corr-replay: $(CORRREPLAY)
-
-# adapter/InitialAlignment_harris_mi355x.cpp (InitialAlignment::obtainHarrisKeypoints) compiled the same way:
-# the InitialAlignment.h and Filter.h of tests/adapter_standins_harris in front (the class with that private
-# member and its radius_factor_; Filter::extractIndices, which the member ends in), linked with a driver that
-# calls it on a cloud file and a normals file (test infrastructure)
-STANDIN_HAR := tests/adapter_standins_harris
-HARREPLAY   := adapter/build/replay_test_harris
-$(HARREPLAY): adapter/InitialAlignment_harris_mi355x.cpp include/mi355x_gicp.h $(wildcard $(STANDIN)/*.h) \
-              $(wildcard $(STANDIN_NRM)/*.h) $(wildcard $(STANDIN_HAR)/*.h) $(STANDIN)/Utils_standin.cpp \
-              $(STANDIN_HAR)/replay_test_harris.cpp $(LIB)
-	mkdir -p adapter/build
-	g++ -O2 -std=c++14 -Wall -Wextra -Werror -I$(STANDIN_HAR) -I$(STANDIN_NRM) -I$(STANDIN) -Iadapter -Iinclude -o $@ \
-	    adapter/InitialAlignment_harris_mi355x.cpp $(STANDIN)/Utils_standin.cpp $(STANDIN_HAR)/replay_test_harris.cpp \
-	    -L$(PKG) -lmgicp -Wl,-rpath,'$$ORIGIN/../../$(PKG)'
-
-harris-replay: $(HARREPLAY)
+# adapter/GICPAlignment.cpp + adapter/Filter_mi355x.cpp: a replay of test/test_gicp_alignment.cpp:50-131
+$(eval $(call replay_rule,adapter-replay,replay_test_gicp_alignment,adapter/GICPAlignment.cpp adapter/Filter_mi355x.cpp,\
+  $(STANDIN),$(STANDIN)/Utils_standin.cpp $(STANDIN)/replay_test_gicp_alignment.cpp))
+# adapter/FODDetector_mi355x.cpp (FODDetector::clusterPossibleFODs): FODDetector.h, pcl::PointIndices and the
+# members the adapter leaves alone in front; a replay of test/test_fod_detector.cpp's testFODClustering and
+# testEmptyCloud
+$(eval $(call replay_rule,fod-replay,replay_test_fod_detector,adapter/FODDetector_mi355x.cpp,$(STANDIN_FOD) $(STANDIN),\
+  $(STANDIN)/Utils_standin.cpp $(STANDIN_FOD)/FODDetector_standin.cpp $(STANDIN_FOD)/replay_test_fod_detector.cpp))
+# adapter/Utils_mi355x.cpp (Utils::getNormals): the Utils.h with getNormals and a layout-exact pcl::Normal in
+# front; a driver that runs it as InitialAlignment's constructor does
+$(eval $(call replay_rule,normals-replay,replay_test_normals,adapter/Utils_mi355x.cpp,$(STANDIN_NRM) $(STANDIN),\
+  $(STANDIN)/Utils_standin.cpp $(STANDIN_NRM)/replay_test_normals.cpp))
+# adapter/InitialAlignment_mi355x.cpp (obtainBoundaryKeypoints, obtainHarrisKeypoints, obtainFeatures,
+# obtainCorrespondences): the InitialAlignment.h and Filter.h of tests/adapter_standins_ia in front, then the
+# Utils.h with pcl::Normal; one driver per member, each on files of its inputs, and one that runs the four
+# members in one process
+IA_REPLAYS := boundary-replay:replay_test_boundary fpfh-replay:replay_test_fpfh corr-replay:replay_test_correspondences \
+              harris-replay:replay_test_harris ia-replay:replay_test_initial_alignment
+$(foreach r,$(IA_REPLAYS),$(eval $(call replay_rule,$(word 1,$(subst :, ,$(r))),$(word 2,$(subst :, ,$(r))),\
+  adapter/InitialAlignment_mi355x.cpp,$(STANDIN_IA) $(STANDIN_NRM) $(STANDIN),\
+  $(STANDIN)/Utils_standin.cpp $(STANDIN_IA)/Filter_standin.cpp $(STANDIN_IA)/$(word 2,$(subst :, ,$(r))).cpp)))
 
 oracle:
 	$(MAKE) -C oracle
@@ -153,4 +86,4 @@ clean:
 	rm -f $(LIB) $(PKG)/libmgicp_*.so $(OBJS)
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle clean adapter-example adapter-replay fod-replay normals-replay boundary-replay fpfh-replay corr-replay harris-replay variant
+.PHONY: all oracle clean adapter-example adapter-replay fod-replay normals-replay boundary-replay fpfh-replay corr-replay harris-replay ia-replay variant

@@ -9,45 +9,23 @@
  */
 #include <FODDetector.h>
 
+#include <EngineContext_mi355x.h>
 #include <mi355x_gicp.h>
 
 #include <cstddef>
-#include <mutex>
 #include <vector>
 
 namespace
 {
 static_assert(sizeof(pcl::PointXYZRGB) == 32, "PointXYZRGB record must be 32 bytes (x,y,z,pad,rgb,pad)");
-
-// one engine context per process for this helper; a context serves one caller at a time
-// (include/mi355x_gicp.h "Threading"), so every use takes the mutex
-std::mutex& fodMutex()
-{
-    static std::mutex m;
-    return m;
-}
-
-mgicp_ctx* fodContext()
-{
-    static mgicp_ctx* ctx = []() {
-        mgicp_ctx* c = nullptr;
-        if (mgicp_create(&c, nullptr) != MGICP_OK)
-        {
-            ROS_ERROR("MI355X engine unavailable: no HIP device?");
-            return static_cast<mgicp_ctx*>(nullptr);
-        }
-        return c;
-    }();
-    return ctx;
-}
 }  // namespace
 
 void FODDetector::clusterPossibleFODs()
 {
     cluster_indices_.clear();
     const size_t n = cloud_ ? cloud_->points.size() : 0;
-    std::lock_guard<std::mutex> lock(fodMutex());
-    mgicp_ctx* ctx = fodContext();
+    std::lock_guard<std::mutex> lock(mi355x::helperMutex());
+    mgicp_ctx* ctx = mi355x::helperContext();
     if (!ctx)
         return;
     // EuclideanClusterExtraction::setMinClusterSize(int): the double is truncated.  The conversion is

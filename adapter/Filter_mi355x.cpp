@@ -11,40 +11,16 @@
 #include <Filter.h>
 #include <Utils.h>
 
+#include <EngineContext_mi355x.h>
 #include <mi355x_gicp.h>
 
 #include <cstddef>
-#include <mutex>
 #include <vector>
 
 namespace
 {
 static_assert(sizeof(pcl::PointXYZRGB) == 32, "PointXYZRGB record must be 32 bytes (x,y,z,pad,rgb,pad)");
 constexpr int kRgbOffset = offsetof(pcl::PointXYZRGB, rgba);
-
-// one engine context per process for the stateless helpers (mgicp_create resolves every kernel).
-// A context holds mutable scratch and one stream and serves one caller at a time
-// (include/mi355x_gicp.h "Threading"): every use takes helperMutex(), so concurrent ROS
-// callbacks (a multi-threaded spinner) serialise on it instead of racing.
-std::mutex& helperMutex()
-{
-    static std::mutex m;
-    return m;
-}
-
-mgicp_ctx* helperContext()
-{
-    static mgicp_ctx* ctx = []() {
-        mgicp_ctx* c = nullptr;
-        if (mgicp_create(&c, nullptr) != MGICP_OK)
-        {
-            ROS_ERROR("MI355X engine unavailable: no HIP device?");
-            return static_cast<mgicp_ctx*>(nullptr);
-        }
-        return c;
-    }();
-    return ctx;
-}
 }  // namespace
 
 void Filter::downsampleCloud(PointCloudRGB::Ptr cloud, PointCloudRGB::Ptr cloud_downsampled)
@@ -53,8 +29,8 @@ void Filter::downsampleCloud(PointCloudRGB::Ptr cloud, PointCloudRGB::Ptr cloud_
     double res = Utils::computeCloudResolution(cloud);
     ROS_INFO("Pointcloud resolution before downsampling: %f", res);
 
-    std::lock_guard<std::mutex> lock(helperMutex());
-    mgicp_ctx* ctx = helperContext();
+    std::lock_guard<std::mutex> lock(mi355x::helperMutex());
+    mgicp_ctx* ctx = mi355x::helperContext();
     if (!ctx)
         return;
     // the reference passes the leaf through Eigen::Vector4f: round to float first
@@ -87,8 +63,8 @@ void Filter::removeFromCloud(PointCloudRGB::Ptr input_cloud, PointCloudRGB::Ptr 
                              PointCloudRGB::Ptr cloud_filtered)
 {
     ROS_INFO("Difference from segment with threshold: %f", threshold);
-    std::lock_guard<std::mutex> lock(helperMutex());
-    mgicp_ctx* ctx = helperContext();
+    std::lock_guard<std::mutex> lock(mi355x::helperMutex());
+    mgicp_ctx* ctx = mi355x::helperContext();
     if (!ctx)
         return;
     const size_t n = input_cloud->points.size();

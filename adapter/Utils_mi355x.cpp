@@ -10,10 +10,10 @@
  */
 #include <Utils.h>
 
+#include <EngineContext_mi355x.h>
 #include <mi355x_gicp.h>
 
 #include <cstddef>
-#include <mutex>
 #include <vector>
 
 namespace
@@ -21,28 +21,6 @@ namespace
 static_assert(sizeof(pcl::PointXYZRGB) == 32, "PointXYZRGB record must be 32 bytes (x,y,z,pad,rgb,pad)");
 static_assert(sizeof(pcl::Normal) == 32, "pcl::Normal record must be 32 bytes (normal[3], pad, curvature, pad)");
 static_assert(offsetof(pcl::Normal, curvature) == 16, "pcl::Normal::curvature sits at byte 16");
-
-// one engine context per process for this helper; a context serves one caller at a time
-// (include/mi355x_gicp.h "Threading"), so every use takes the mutex
-std::mutex& normalsMutex()
-{
-    static std::mutex m;
-    return m;
-}
-
-mgicp_ctx* normalsContext()
-{
-    static mgicp_ctx* ctx = []() {
-        mgicp_ctx* c = nullptr;
-        if (mgicp_create(&c, nullptr) != MGICP_OK)
-        {
-            ROS_ERROR("MI355X engine unavailable: no HIP device?");
-            return static_cast<mgicp_ctx*>(nullptr);
-        }
-        return c;
-    }();
-    return ctx;
-}
 }  // namespace
 
 bool Utils::getNormals(PointCloudRGB::Ptr& cloud, double normal_radius, PointCloudNormal::Ptr& normals)
@@ -53,8 +31,8 @@ bool Utils::getNormals(PointCloudRGB::Ptr& cloud, double normal_radius, PointClo
     normals->header = cloud ? cloud->header : pcl::PCLHeader();
     normals->points.clear();
     normals->width = normals->height = 0;
-    std::lock_guard<std::mutex> lock(normalsMutex());
-    mgicp_ctx* ctx = normalsContext();
+    std::lock_guard<std::mutex> lock(mi355x::helperMutex());
+    mgicp_ctx* ctx = mi355x::helperContext();
     if (ctx)
     {
         std::vector<pcl::Normal> out(n);  // data_n[3] = 0 and the pads from the constructor

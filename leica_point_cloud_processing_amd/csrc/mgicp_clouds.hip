@@ -605,6 +605,20 @@ int mgicp::build_grid(mgicp_ctx* ctx, Cloud& cl, bool defer_extras) {
   return defer_extras ? MGICP_OK : build_grid_extras(ctx, cl);
 }
 
+// Upload a cloud into ctx->aux and build its grid over the finite points (the reference's KdTreeFLANN
+// holds only those); force_h > 0: with that cell edge.  Both flags are the call's own and are back at
+// their defaults on every return.  An empty grid (no finite point) is not an error: callers check aux.n.
+int mgicp::aux_grid(mgicp_ctx* ctx, const float* xyz, size_t n, size_t stride, double force_h) {
+  int rc = upload_cloud(ctx, ctx->aux, xyz, n, stride, false);
+  if (rc) return rc;
+  ctx->aux.drop_nonfinite = true;
+  ctx->aux.force_h = force_h;
+  rc = build_grid(ctx, ctx->aux);
+  ctx->aux.drop_nonfinite = false;
+  ctx->aux.force_h = 0.0;
+  return rc;
+}
+
 // query order of the shard's 1-NN sweeps and source covariances (once per source cloud and shard)
 const uint32_t* mgicp::query_perm(mgicp_ctx* ctx) {
   if (ctx->qperm_aux) {  // sorted on the aux stream at set_source: the main stream waits for it on the device

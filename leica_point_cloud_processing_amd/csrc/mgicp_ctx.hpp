@@ -1,5 +1,5 @@
 // mgicp_ctx.hpp -- the context and the host helpers that libmgicp.so's host translation units share:
-// mgicp_engine.hip, mgicp_clouds.hip, mgicp_pass.hip, mgicp_fod.hip and mgicp_comm.hip (the product calls
+// mgicp_engine.hip, mgicp_clouds.hip, mgicp_pass.hip, mgicp_fod.hip, mgicp_features.hip and mgicp_comm.hip (the product calls
 // of include/mi355x_gicp.h, by subsystem) and mgicp_debug.hip (the test, benchmark and diagnostic calls
 // of include/mi355x_gicp_debug.h).  Private: nothing here crosses the C-ABI, and the
 // export map (libmgicp.map) keeps every name below out of the library's dynamic symbol table.
@@ -9,6 +9,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -121,6 +122,13 @@ struct DevBuf {
     p = nullptr;
     cap = 0;
   }
+};
+
+// a function-local device buffer, released on every exit.  (DevBuf itself has no destructor: the target
+// cache's buffers are globals and would call hipFree at process exit.)
+template <class T>
+struct ScopedBuf : DevBuf<T> {
+  ~ScopedBuf() { this->release(); }
 };
 
 struct Cloud {
@@ -590,6 +598,7 @@ int upload_cloud(mgicp_ctx* ctx, Cloud& cl, const float* xyz, size_t n, size_t s
 int bbox_to_host(mgicp_ctx* ctx, const float4* pts, size_t n, float lo[3], float hi[3], double* bad = nullptr,
                  const char* queued = nullptr);
 int build_grid(mgicp_ctx* ctx, Cloud& cl, bool defer_extras = false);
+int aux_grid(mgicp_ctx* ctx, const float* xyz, size_t n, size_t stride, double force_h = 0.0);
 const uint32_t* query_perm(mgicp_ctx* ctx);
 int cov_join_all(mgicp_ctx* ctx);
 int cov_prep_async_all(mgicp_ctx* ctx);
@@ -598,6 +607,17 @@ int target_cov(mgicp_ctx* ctx);
 int cov_lazy(mgicp_ctx* ctx);
 void tcache_donate(mgicp_ctx* ctx, bool cov_complete);
 int tcache_adopt(mgicp_ctx* ctx);
+
+// FLANN's radius search as the product calls restate it: d2 < r2 = float(radius^2), strict, so 0 links
+// nothing, not even a point with itself.  Every neighbour lies within `reach` per axis; a denormal r2
+// may be far above radius^2
+struct FlannRadius {
+  float r2;
+  double reach;
+  explicit FlannRadius(double radius) : r2(static_cast<float>(radius * radius)), reach(radius) {
+    if (r2 < 1.17549435e-38f) reach = std::max(reach, std::sqrt(static_cast<double>(r2)));
+  }
+};
 
 // ---- mgicp_engine.hip: the align loop's steps that the debug entry points call too (documented there) ----
 int prepare(mgicp_ctx* ctx, bool need_cov);

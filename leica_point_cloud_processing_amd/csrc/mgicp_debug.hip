@@ -2,7 +2,7 @@
 // (include/mi355x_gicp_debug.h): introspection for the parity tests, pass timing and counters for
 // bench.py, and the per-context switches between the engine's forms.  Not part of the drop-in: the
 // product calls of include/mi355x_gicp.h live in mgicp_engine.hip and the host files beside it
-// (mgicp_clouds.hip, mgicp_pass.hip, mgicp_fod.hip, mgicp_comm.hip), whose helpers these reach through
+// (mgicp_clouds.hip, mgicp_pass.hip, mgicp_fod.hip, mgicp_features.hip, mgicp_comm.hip), whose helpers these reach through
 // mgicp_ctx.hpp.
 #pragma clang fp contract(off)
 

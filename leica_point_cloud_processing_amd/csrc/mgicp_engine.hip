@@ -11,7 +11,7 @@
 // total), or -- without that segment -- one RCCL all-gather of super partials per pass (xGMI).
 // This file: the context's life, the sweeps, the two solvers' outer steps and mgicp_align.  The clouds
 // and their grids / covariances are in mgicp_clouds.hip, the objective passes in mgicp_pass.hip, the
-// transports in mgicp_comm.hip, the calls beside the alignment in mgicp_fod.hip.
+// transports in mgicp_comm.hip, the calls beside the alignment in mgicp_fod.hip and mgicp_features.hip.
 #pragma clang fp contract(off)
 
 #include <hip/hip_runtime.h>

@@ -3479,6 +3479,73 @@ __global__ void radius_keep_kernel(GridView g, size_t n, float r2, int need,
 }
 
 // ------------------------------------------------------------------------------------
+// What the radius walks of the feature kernels share (normals, FPFH, Harris): the cell box of a radius,
+// the range of one of its rows, and the slotted counters.
+// ------------------------------------------------------------------------------------
+// The cells that can hold a point within sqrt(r2) of any query in [lo, hi]: the bounding box widened by
+// rx = sqrtf(r2) * 1.0001f + slop, then the cells of its corners (bcell, the very function that assigned
+// every point its cell).
+// Exactness, for any h (DESIGN.md has the long form): a pair passes the float test only
+// if dx^2 < r2 as real numbers for the ROUNDED difference dx = fl(q.x - p.x) (rounding is monotone and
+// r2 is a float), so |dx| < sqrt(r2) <= sqrtf(r2) (1 + 2^-24) and |q.x - p.x| <= |dx| (1 + 2^-24).  With
+// lo <= q.x the float fl(lo - rx) is at most p.x: the 1e-4 margin covers the three roundings relative
+// to rx, the slop (>= 2^-20 of the largest coordinate) the rounding of the difference relative to lo.
+// bcell is monotone (a rounded subtraction, a rounded product by inv_h > 0, floor, clamps), so
+// bcell(p.x) >= bcell(fl(lo - rx)); the upper side and the other axes alike.  An infinite rx gives
+// the whole grid.
+struct CellBox {
+  int xa, xb, ya, yb, za, zb;
+};
+
+__device__ __forceinline__ CellBox cell_box(const GridView& g, const float (&lo)[3], const float (&hi)[3], float r2) {
+  const float rx = sqrtf(r2) * 1.0001f + g.slop;
+  CellBox b;
+  b.xa = bcell(lo[0] - rx, g.ox, g.inv_h, g.nx);
+  b.xb = bcell(hi[0] + rx, g.ox, g.inv_h, g.nx);
+  b.ya = bcell(lo[1] - rx, g.oy, g.inv_h, g.ny);
+  b.yb = bcell(hi[1] + rx, g.oy, g.inv_h, g.ny);
+  b.za = bcell(lo[2] - rx, g.oz, g.inv_h, g.nz);
+  b.zb = bcell(hi[2] + rx, g.oz, g.inv_h, g.nz);
+  return b;
+}
+
+// the box of a single query
+__device__ __forceinline__ CellBox cell_box(const GridView& g, const float4& q, float r2) {
+  const float at[3] = {q.x, q.y, q.z};
+  return cell_box(g, at, at, r2);
+}
+
+// a value every lane of the wave holds, moved to a scalar register
+__device__ __forceinline__ int wave_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+
+__device__ __forceinline__ CellBox wave_uniform(const CellBox& b) {
+  return CellBox{wave_uniform(b.xa), wave_uniform(b.xb), wave_uniform(b.ya), wave_uniform(b.yb),
+                 wave_uniform(b.za), wave_uniform(b.zb)};
+}
+
+// row (z, y) of the box: its points are the sorted positions [ja, jb).  Every walk takes the rows by
+// ascending z then y and the positions ascending within a row.
+__device__ __forceinline__ void box_row(const GridView& g, const CellBox& b, int z, int y, uint32_t& ja,
+                                        uint32_t& jb) {
+  const uint32_t* row = g.cell_start + (static_cast<size_t>(z) * g.ny + y) * g.nx;
+  ja = row[b.xa];
+  jb = row[b.xb + 1];
+}
+
+// Slotted counters: ctr holds `slots` groups of W words and lane 0 adds v to the group of index modulo
+// the slots, zero values skipped -- one address for every wave's add costs more than the kernels' work
+// (65536 waves took 0.8 ms to add one word each); the host sums the slots by column.
+template <int W, class Index>
+__device__ __forceinline__ void slot_add(unsigned long long* __restrict__ ctr, Index index, int slots, int lane,
+                                         const unsigned long long (&v)[W]) {
+  if (lane != 0) return;
+  unsigned long long* slot = ctr + W * (index % slots);
+#pragma unroll
+  for (int k = 0; k < W; ++k)
+    if (v[k]) atomicAdd(slot + k, v[k]);
+}
+
+// ------------------------------------------------------------------------------------
 // Radius normals (pcl::NormalEstimation with a radius search, as Utils::getNormals calls it):
 // the cell-cooperative, LDS-staged tile search -- DESIGN.md "Radius normals".
 // ------------------------------------------------------------------------------------
@@ -3487,27 +3554,16 @@ __global__ void radius_keep_kernel(GridView g, size_t n, float r2, int need,
 // group by group: a group is the run of its queries that share the leader's cell row (y, z) and lie
 // within kNrmRunCells cells of the leader along x.  For a group the block
 //   1. reduces the bounding box of the group's query coordinates,
-//   2. widens it by rx = sqrtf(r2) * 1.0001f + slop and takes the cells of its corners (bcell, the very
-//      function that assigned every point its cell): the group's cell box,
+//   2. takes the cell box of that bounding box (cell_box, made wave-uniform),
 //   3. streams the box's rows -- each one contiguous range of pts -- through the LDS stage in chunks of
 //      kNrmStage points (16-byte loads, rows packed back to back), and after each chunk every lane of
 //      the group tests the staged points against its own query: one LDS address per wave (broadcast).
-// Exactness of the cell box, for any h (DESIGN.md has the long form): a pair passes the float test only
-// if dx^2 < r2 as real numbers for the ROUNDED difference dx = fl(q.x - p.x) (rounding is monotone and
-// r2 is a float), so |dx| < sqrt(r2) <= sqrtf(r2) (1 + 2^-24) and |q.x - p.x| <= |dx| (1 + 2^-24).  With
-// lo <= q.x the float fl(lo - rx) is at most p.x: the 1e-4 margin covers the three roundings relative
-// to rx, the slop (>= 2^-20 of the largest coordinate) the rounding of the difference relative to lo.
-// bcell is monotone (a rounded subtraction, a rounded product by inv_h > 0, floor, clamps), so
-// bcell(p.x) >= bcell(fl(lo - rx)); the upper side and the other axes alike.  An infinite rx gives
-// the whole grid.
 // Order of the sums: rows ascend in z then y and positions ascend within a row, so a lane meets its
 // neighbours in ascending sorted position whatever the grouping and chunking -- the same bits every call.
 constexpr int kNrmThreads = 64;   // queries per block: one wave (measured against 128 and 256)
 constexpr int kNrmStage = 512;    // points per staged chunk (8 KiB of LDS)
 constexpr int kNrmRunCells = 3;  // x-adjacent cells one group may span
 constexpr int kNrmBatch = 8;     // staged points a lane reads and tests before it adds the hits
-
-__device__ __forceinline__ int nrm_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
 __global__ __launch_bounds__(kNrmThreads) void normals_tile_kernel(GridView g, size_t n, float r2, float vx, float vy,
                                                                    float vz, float4* __restrict__ out_orig,
@@ -3525,7 +3581,6 @@ __global__ __launch_bounds__(kNrmThreads) void normals_tile_kernel(GridView g, s
   const int cx = bcell(q.x, g.ox, g.inv_h, g.nx), cy = bcell(q.y, g.oy, g.inv_h, g.ny),
             cz = bcell(q.z, g.oz, g.inv_h, g.nz);
   const double qx = static_cast<double>(q.x), qy = static_cast<double>(q.y), qz = static_cast<double>(q.z);
-  const float rx = sqrtf(r2) * 1.0001f + g.slop;
   // first moments s0..s2 and second moments (xx xy xz yy yz zz) of p - q over the neighbours
   double s0 = 0.0, s1 = 0.0, s2 = 0.0, sxx = 0.0, sxy = 0.0, sxz = 0.0, syy = 0.0, syz = 0.0, szz = 0.0;
   int m = 0;
@@ -3565,9 +3620,7 @@ __global__ __launch_bounds__(kNrmThreads) void normals_tile_kernel(GridView g, s
         hi[d] = fmaxf(hi[d], box[w][3 + d]);
       }
     }
-    const int xa = nrm_uniform(bcell(lo[0] - rx, g.ox, g.inv_h, g.nx)), xb = nrm_uniform(bcell(hi[0] + rx, g.ox, g.inv_h, g.nx));
-    const int ya = nrm_uniform(bcell(lo[1] - rx, g.oy, g.inv_h, g.ny)), yb = nrm_uniform(bcell(hi[1] + rx, g.oy, g.inv_h, g.ny));
-    const int za = nrm_uniform(bcell(lo[2] - rx, g.oz, g.inv_h, g.nz)), zb = nrm_uniform(bcell(hi[2] + rx, g.oz, g.inv_h, g.nz));
+    const CellBox cells = wave_uniform(cell_box(g, lo, hi, r2));
     const unsigned long long wave_in = static_cast<unsigned long long>(__popcll(__ballot(in)));
     // the lanes of the group against stage[0 .. fill)
     auto add = [&](const float4& pj) {
@@ -3609,11 +3662,12 @@ __global__ __launch_bounds__(kNrmThreads) void normals_tile_kernel(GridView g, s
       __syncthreads();
     };
     int fill = 0;
-    for (int z = za; z <= zb; ++z) {
-      for (int y = ya; y <= yb; ++y) {
-        const uint32_t* row = g.cell_start + (static_cast<size_t>(z) * g.ny + y) * g.nx;
-        uint32_t a = static_cast<uint32_t>(nrm_uniform(static_cast<int>(row[xa])));
-        const uint32_t b = static_cast<uint32_t>(nrm_uniform(static_cast<int>(row[xb + 1])));
+    for (int z = cells.za; z <= cells.zb; ++z) {
+      for (int y = cells.ya; y <= cells.yb; ++y) {
+        uint32_t ja, jb;
+        box_row(g, cells, z, y, ja, jb);
+        uint32_t a = static_cast<uint32_t>(wave_uniform(static_cast<int>(ja)));
+        const uint32_t b = static_cast<uint32_t>(wave_uniform(static_cast<int>(jb)));
         while (a < b) {
           const uint32_t take = min(b - a, static_cast<uint32_t>(kNrmStage - fill));
           for (uint32_t i = static_cast<uint32_t>(t); i < take; i += kNrmThreads) stage[fill + i] = g.pts[a + i];
@@ -4005,8 +4059,7 @@ __global__ __launch_bounds__(64, 1) void boundary_wave_kernel(GridView g, size_t
 // calls it) -- DESIGN.md "FPFH".
 // ------------------------------------------------------------------------------------
 // One wave per item throughout (a block is one wave, so __syncthreads orders its LDS traffic): the wave
-// takes the item's cell box -- the box of normals_tile_kernel for a single query, exact for any cell
-// edge by the same argument -- through fpfh_walk, 64 candidates a turn.
+// takes the item's cell box (cell_box, made wave-uniform) through fpfh_walk, 64 candidates a turn.
 //   fpfh_mark_kernel   item = keypoint: mark[j] = 1 for every member j of its set (same-value stores);
 //                      the marked positions are then listed by an exclusive scan (fpfh_list_kernel)
 //   fpfh_spfh_kernel   item = listed record: d2 first, the pair features only for members; the 33 bin
@@ -4022,38 +4075,22 @@ constexpr uint32_t kFpfhNone = 0xffffffffu;
 constexpr int kFpfhMaxSet = 65535;  // rows are uint16 counts
 constexpr size_t kFpfhMaxBlocks = 16384;  // one-wave blocks per launch (8 per SIMD); items beyond go round in a grid stride
 
-struct FpfhBox {
-  int xa, xb, ya, yb, za, zb;
-};
-
-__device__ __forceinline__ FpfhBox fpfh_box(const GridView& g, const float4& q, float r2) {
-  const float rx = sqrtf(r2) * 1.0001f + g.slop;
-  FpfhBox b;
-  b.xa = nrm_uniform(bcell(q.x - rx, g.ox, g.inv_h, g.nx));
-  b.xb = nrm_uniform(bcell(q.x + rx, g.ox, g.inv_h, g.nx));
-  b.ya = nrm_uniform(bcell(q.y - rx, g.oy, g.inv_h, g.ny));
-  b.yb = nrm_uniform(bcell(q.y + rx, g.oy, g.inv_h, g.ny));
-  b.za = nrm_uniform(bcell(q.z - rx, g.oz, g.inv_h, g.nz));
-  b.zb = nrm_uniform(bcell(q.z + rx, g.oz, g.inv_h, g.nz));
-  return b;
-}
-
 // f(j, ok) for every lane and every turn (ok: j is a candidate), so f may ballot and shuffle.  The box's
 // rows of cells, (z, y) ascending, are taken 64 at a time: lane l loads the range of row l, a wave prefix
 // sum lays the ranges end to end, and the candidates are dealt out 64 a turn in that order -- ascending
 // row, then ascending sorted position -- so a turn costs one round of point loads whatever the number of
 // rows it spans (a box of 3 x 3 rows with a few points each, the reference's radius, is one turn)
 template <class F>
-__device__ __forceinline__ void fpfh_walk(const GridView& g, const FpfhBox& b, int lane, F&& f) {
+__device__ __forceinline__ void fpfh_walk(const GridView& g, const CellBox& b, int lane, F&& f) {
   const int ys = b.yb - b.ya + 1;
   const int nrows = (b.zb - b.za + 1) * ys;
   for (int r0 = 0; r0 < nrows; r0 += 64) {
     const int r = r0 + lane;
     uint32_t a = 0, len = 0;
     if (r < nrows) {
-      const uint32_t* row = g.cell_start + (static_cast<size_t>(b.za + r / ys) * g.ny + (b.ya + r % ys)) * g.nx;
-      a = row[b.xa];
-      len = row[b.xb + 1] - a;
+      uint32_t e;
+      box_row(g, b, b.za + r / ys, b.ya + r % ys, a, e);
+      len = e - a;
     }
     uint32_t end = len;  // inclusive prefix sum over the lanes
 #pragma unroll
@@ -4091,7 +4128,7 @@ __global__ __launch_bounds__(64) void fpfh_mark_kernel(GridView g, const int* __
     const uint32_t p = pos_of[kp ? static_cast<size_t>(kp[k]) : k];
     if (p == kFpfhNone) continue;
     const float4 q = g.pts[p];
-    const FpfhBox box = fpfh_box(g, q, r2);
+    const CellBox box = wave_uniform(cell_box(g, q, r2));
     int m = 0;
     fpfh_walk(g, box, lane, [&](uint32_t j, bool ok) {
       const bool member = ok && dist2(q.x, q.y, q.z, g.pts[j]) < r2;
@@ -4101,7 +4138,7 @@ __global__ __launch_bounds__(64) void fpfh_mark_kernel(GridView g, const int* __
     });
     if (lane == 0 && m > kFpfhMaxSet) *too_big = 1u;  // the later steps then leave at once
   }
-  if (lane == 0 && tests) atomicAdd(ctr + 2 * (blockIdx.x % kFpfhCtrSlots), tests);
+  slot_add(ctr, blockIdx.x, kFpfhCtrSlots, lane, {tests, 0ull});
 }
 
 __global__ void fpfh_list_kernel(const uint32_t* __restrict__ mark, const uint32_t* __restrict__ pos, size_t n,
@@ -4146,9 +4183,8 @@ __device__ __forceinline__ bool fpfh_pair_bins(const float4& pi, float nix, floa
   return true;
 }
 
-// ctr: kFpfhCtrSlots pairs of {pair tests, pair features}, a block adding to the pair of its index modulo
-// the slots -- one address for every wave's add costs more than the kernels' work (65536 waves took
-// 0.8 ms to add one word each); the host sums the slots.  *too_big = 1 when a set exceeds kFpfhMaxSet -- the call then
+// ctr: kFpfhCtrSlots pairs of {pair tests, pair features}, a block adding to the pair of its index
+// (slot_add).  *too_big = 1 when a set exceeds kFpfhMaxSet -- the call then
 // fails, so a wave that finds the flag set (by the mark step or by another row) stops
 __global__ __launch_bounds__(64) void fpfh_spfh_kernel(GridView g, const uint32_t* __restrict__ list,
                                                        const uint32_t* __restrict__ count,
@@ -4168,7 +4204,7 @@ __global__ __launch_bounds__(64) void fpfh_spfh_kernel(GridView g, const uint32_
     const float nix = normals[3 * oi], niy = normals[3 * oi + 1], niz = normals[3 * oi + 2];
     if (lane < kFpfhBins) hist[lane] = 0;
     __syncthreads();
-    const FpfhBox box = fpfh_box(g, q, r2);
+    const CellBox box = wave_uniform(cell_box(g, q, r2));
     int m = 0;
     fpfh_walk(g, box, lane, [&](uint32_t j, bool ok) {
       bool member = false, feat = false;
@@ -4199,8 +4235,7 @@ __global__ __launch_bounds__(64) void fpfh_spfh_kernel(GridView g, const uint32_
     }
     __syncthreads();
   }
-  if (lane == 0 && tests) atomicAdd(ctr + 2 * (blockIdx.x % kFpfhCtrSlots), tests);
-  if (lane == 0 && feats) atomicAdd(ctr + 2 * (blockIdx.x % kFpfhCtrSlots) + 1, feats);
+  slot_add(ctr, blockIdx.x, kFpfhCtrSlots, lane, {tests, feats});
 }
 
 __global__ __launch_bounds__(64) void fpfh_final_kernel(GridView g, const int* __restrict__ kp, size_t nk,
@@ -4222,7 +4257,7 @@ __global__ __launch_bounds__(64) void fpfh_final_kernel(GridView g, const int* _
       continue;
     }
     const float4 q = g.pts[p];
-    const FpfhBox box = fpfh_box(g, q, r2);
+    const CellBox box = wave_uniform(cell_box(g, q, r2));
     float acc = 0.f;
     fpfh_walk(g, box, lane, [&](uint32_t j, bool ok) {
       const float d2 = ok ? dist2(q.x, q.y, q.z, g.pts[j]) : INFINITY;
@@ -4250,7 +4285,7 @@ __global__ __launch_bounds__(64) void fpfh_final_kernel(GridView g, const int* _
     if (sum != 0.f) acc = acc * (100.f / sum);
     if (lane < kFpfhBins) o[lane] = acc;
   }
-  if (lane == 0 && tests) atomicAdd(ctr + 2 * (blockIdx.x % kFpfhCtrSlots), tests);
+  slot_add(ctr, blockIdx.x, kFpfhCtrSlots, lane, {tests, 0ull});
 }
 
 // ------------------------------------------------------------------------------------
@@ -4265,32 +4300,16 @@ __global__ __launch_bounds__(64) void fpfh_final_kernel(GridView g, const int* _
 //                           first larger neighbour; a wave without candidates leaves at once, and a wave's
 //                           walk ends with its last lane (the loop is per lane, so the exec mask is the
 //                           ballot)
-// A lane takes its cell box -- har_box, the box of normals_tile_kernel for a single query, exact for any
-// cell edge by the same argument -- row by row, (z, y) ascending and positions ascending within a row: a
+// A lane takes its cell box (cell_box, lane-private) row by row, (z, y) ascending and positions ascending
+// within a row: a
 // fixed order, so the fp64 sums have the same bits on every call.  A record whose box holds more than
 // kHarLaneCap candidates (known before a row is walked: the box's rows are added up as they come) is
 // listed instead and taken by a wave in the hand-off launch (harris_*_wave_kernel): row by row again,
 // lane l taking the row's positions l, l + 64, ..., the lanes' sums then through wave_sum's tree --
 // another fixed order, and the path of a record depends on the cloud and the radius alone.
 // ctr: kHarCtrSlots triples {pair tests, candidates, tied keypoints}, a wave adding to the triple of its
-// index modulo the slots (the FPFH kernels' reason); the host sums the slots.
+// index (slot_add).
 constexpr uint32_t kHarLaneCap = 512;  // candidates of a box a lane walks itself
-
-struct HarBox {
-  int xa, xb, ya, yb, za, zb;
-};
-
-__device__ __forceinline__ HarBox har_box(const GridView& g, const float4& q, float r2) {
-  const float rx = sqrtf(r2) * 1.0001f + g.slop;
-  HarBox b;
-  b.xa = bcell(q.x - rx, g.ox, g.inv_h, g.nx);
-  b.xb = bcell(q.x + rx, g.ox, g.inv_h, g.nx);
-  b.ya = bcell(q.y - rx, g.oy, g.inv_h, g.ny);
-  b.yb = bcell(q.y + rx, g.oy, g.inv_h, g.ny);
-  b.za = bcell(q.z - rx, g.oz, g.inv_h, g.nz);
-  b.zb = bcell(q.z + rx, g.oz, g.inv_h, g.nz);
-  return b;
-}
 
 // a neighbour's normal into the count and the sums: PCL counts by normal_x alone
 __device__ __forceinline__ void har_add(const float4& nj, int& c, double (&S)[6]) {
@@ -4337,12 +4356,7 @@ __device__ __forceinline__ void har_count(unsigned long long* __restrict__ ctr, 
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) tests += __shfl_down(tests, off, 64);
   const unsigned long long nc = __popcll(__ballot(cand)), nt = __popcll(__ballot(tied));
-  if (lane == 0) {
-    unsigned long long* slot = ctr + 3 * (wave % kHarCtrSlots);
-    if (tests) atomicAdd(slot, tests);
-    if (nc) atomicAdd(slot + 1, nc);
-    if (nt) atomicAdd(slot + 2, nt);
-  }
+  slot_add(ctr, wave, kHarCtrSlots, lane, {tests, nc, nt});
 }
 
 __global__ void harris_pack_kernel(const float4* __restrict__ pts, size_t n, const float* __restrict__ normals,
@@ -4365,15 +4379,15 @@ __global__ __launch_bounds__(256) void harris_response_kernel(GridView g, size_t
   bool cand = false;
   if (p < n) {
     const float4 q = g.pts[p];
-    const HarBox b = har_box(g, q, r2);
+    const CellBox b = cell_box(g, q, r2);
     int m = 0, c = 0;
     double S[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     uint32_t seen = 0;
     bool mine = true;
     for (int z = b.za; z <= b.zb && mine; ++z) {
       for (int y = b.ya; y <= b.yb; ++y) {
-        const uint32_t* row = g.cell_start + (static_cast<size_t>(z) * g.ny + y) * g.nx;
-        const uint32_t ja = row[b.xa], jb = row[b.xb + 1];
+        uint32_t ja, jb;
+        box_row(g, b, z, y, ja, jb);
         seen += jb - ja;
         if (seen > kHarLaneCap) {
           mine = false;
@@ -4402,12 +4416,12 @@ __global__ __launch_bounds__(256) void harris_response_kernel(GridView g, size_t
 template <class F, class Stop>
 __device__ __forceinline__ unsigned long long har_wave_rows(const GridView& g, const float4& q, float r2, int lane,
                                                             F&& f, Stop&& stop) {
-  const HarBox b = har_box(g, q, r2);  // q is the wave's: every lane holds the same box
+  const CellBox b = cell_box(g, q, r2);  // q is the wave's: every lane holds the same box
   unsigned long long tests = 0;
   for (int z = b.za; z <= b.zb; ++z) {
     for (int y = b.ya; y <= b.yb; ++y) {
-      const uint32_t* row = g.cell_start + (static_cast<size_t>(z) * g.ny + y) * g.nx;
-      const uint32_t ja = row[b.xa], jb = row[b.xb + 1];
+      uint32_t ja, jb;
+      box_row(g, b, z, y, ja, jb);
       for (uint32_t j = ja + static_cast<uint32_t>(lane); j < jb; j += 64) f(j);
       tests += jb - ja;
       if (stop()) return tests;
@@ -4452,11 +4466,7 @@ __global__ __launch_bounds__(64) void harris_response_wave_kernel(GridView g, co
     if (lane == 0)
       ncand += har_finish(m, c, S, p, __float_as_uint(q.w), thr, resp_pos, resp_orig, covar_orig, count_orig) ? 1 : 0;
   }
-  if (lane == 0) {
-    unsigned long long* slot = ctr + 3 * (blockIdx.x % kHarCtrSlots);
-    if (tests) atomicAdd(slot, tests);
-    if (ncand) atomicAdd(slot + 1, static_cast<unsigned long long>(ncand));
-  }
+  slot_add(ctr, blockIdx.x, kHarCtrSlots, lane, {tests, static_cast<unsigned long long>(ncand), 0ull});
 }
 
 // a candidate is a keypoint unless a member of its set has a larger response (a NaN compares false both
@@ -4474,13 +4484,13 @@ __global__ __launch_bounds__(256) void harris_nms_kernel(GridView g, size_t n, c
   bool tied = false;
   if (cand) {
     const float4 q = g.pts[p];
-    const HarBox b = har_box(g, q, r2);
+    const CellBox b = cell_box(g, q, r2);
     uint32_t seen = 0;
     bool mine = true, top = true;
     for (int z = b.za; z <= b.zb && mine && top; ++z) {
       for (int y = b.ya; y <= b.yb && top; ++y) {
-        const uint32_t* row = g.cell_start + (static_cast<size_t>(z) * g.ny + y) * g.nx;
-        const uint32_t ja = row[b.xa], jb = row[b.xb + 1];
+        uint32_t ja, jb;
+        box_row(g, b, z, y, ja, jb);
         seen += jb - ja;
         if (seen > kHarLaneCap) {
           mine = false;
@@ -4541,11 +4551,7 @@ __global__ __launch_bounds__(64) void harris_nms_wave_kernel(GridView g, const u
       ntied += any_tied ? 1 : 0;
     }
   }
-  if (lane == 0) {
-    unsigned long long* slot = ctr + 3 * (blockIdx.x % kHarCtrSlots);
-    if (tests) atomicAdd(slot, tests);
-    if (ntied) atomicAdd(slot + 2, static_cast<unsigned long long>(ntied));
-  }
+  slot_add(ctr, blockIdx.x, kHarCtrSlots, lane, {tests, 0ull, static_cast<unsigned long long>(ntied)});
 }
 
 // ------------------------------------------------------------------------------------

@@ -1,7 +1,7 @@
 /*
  * TEST INFRASTRUCTURE ONLY -- stand-in of the reference's include/Filter.h for
- * adapter/InitialAlignment_harris_mi355x.cpp: the one static member that adapter calls, with the
- * reference's signature.  Its stand-in body (replay_test_harris.cpp) does what pcl::ExtractIndices does
+ * adapter/InitialAlignment_mi355x.cpp: the one static member that adapter calls, with the
+ * reference's signature.  Its stand-in body (Filter_standin.cpp) does what pcl::ExtractIndices does
  * there: the output becomes the indexed points, in the order of the indices.  <Utils.h> is
  * tests/adapter_standins_normals/Utils.h; pcl::IndicesPtr is a shared pointer to std::vector<int> as in
  * PCL.  This directory comes first on the include path, so <Filter.h> is this file.

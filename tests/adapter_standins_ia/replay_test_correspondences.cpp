@@ -1,7 +1,7 @@
 /*
  * TEST INFRASTRUCTURE ONLY -- drives the adapter's InitialAlignment::obtainCorrespondences
- * (adapter/InitialAlignment_correspondences_mi355x.cpp) as runKeypointsBasedAlgorithm does: the two feature
- * clouds in place and a correspondence vector that already holds entries.
+ * (adapter/InitialAlignment_mi355x.cpp) as runKeypointsBasedAlgorithm does: the two feature clouds in
+ * place and a correspondence vector that already holds entries.
  *
  * usage: replay_test_correspondences <source.bin: 33 float32 per feature> <target.bin: the same>
  *                                    <query.bin: out, int32> <match.bin: out, int32> <distance.bin: out, float32>

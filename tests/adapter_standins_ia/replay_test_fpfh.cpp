@@ -1,7 +1,7 @@
 /*
  * TEST INFRASTRUCTURE ONLY -- drives the adapter's InitialAlignment::obtainFeatures
- * (adapter/InitialAlignment_features_mi355x.cpp) as runKeypointsBasedAlgorithm does: a cloud, its normals,
- * the keypoint indices and a feature cloud that already holds records.
+ * (adapter/InitialAlignment_mi355x.cpp) as runKeypointsBasedAlgorithm does: a cloud, its normals, the
+ * keypoint indices and a feature cloud that already holds records.
  *
  * usage: replay_test_fpfh <cloud.bin: packed float32 xyz> <normals.bin: packed float32 nx ny nz>
  *                         <keypoints.bin: int32> <fpfh.bin: out, 33 float32 per keypoint>

@@ -1,7 +1,7 @@
 /*
  * TEST INFRASTRUCTURE ONLY -- drives the adapter's InitialAlignment::obtainHarrisKeypoints
- * (adapter/InitialAlignment_harris_mi355x.cpp) as runKeypointsBasedAlgorithm does: a cloud, its normals, a
- * keypoint cloud and an index list.
+ * (adapter/InitialAlignment_mi355x.cpp) as runKeypointsBasedAlgorithm does: a cloud, its normals, a keypoint
+ * cloud and an index list.
  *
  * usage: replay_test_harris <cloud.bin: packed float32 xyz> <normals.bin: packed float32 nx ny nz>
  *                           <radius_factor> <keypoints.bin: out, int32>
@@ -15,16 +15,6 @@
 
 typedef pcl::PointCloud<pcl::PointXYZRGB> PointCloudRGB;
 typedef pcl::PointCloud<pcl::Normal> PointCloudNormal;
-
-// pcl::ExtractIndices::filter: the output is replaced by the indexed points
-void Filter::extractIndices(PointCloudRGB::Ptr cloud_in, PointCloudRGB::Ptr cloud_out, pcl::IndicesPtr indices)
-{
-    cloud_out->points.clear();
-    for (std::size_t j = 0; j < indices->size(); ++j)
-        cloud_out->points.push_back(cloud_in->points[static_cast<std::size_t>((*indices)[j])]);
-    cloud_out->width = static_cast<std::uint32_t>(cloud_out->points.size());
-    cloud_out->height = 1;
-}
 
 struct InitialAlignmentReplay
 {

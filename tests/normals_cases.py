@@ -447,7 +447,7 @@ def grid_facts(xyz, radius):
 
 
 def box_facts(xyz, radius):
-    """(rows, points, rx / h) of the cell box of every record taken as a single query (fpfh_box; a group of
+    """(rows, points, rx / h) of the cell box of every record taken as a single query (cell_box; a group of
     normals_tile_kernel has a box at least as large): rows of cells (y, z) and the points inside.  A float32
     restatement of rx = sqrtf(r2) * 1.0001f + slop, slop = 8 maxabs 2^-23 + 1e-6 h, over grid_of's cells.
     Like grid_of it only certifies that a cloud reaches a regime; it never produces an expected result."""

@@ -90,7 +90,8 @@ def test_header_is_plain_c():
 
 def test_drop_in_uses_the_product_header_only():
     """What an integrator compiles and links -- the adapter sources and the C-ABI example -- includes
-    mi355x_gicp.h alone, names no debug hook, and its binaries need no mgicp_* symbol outside that header."""
+    mi355x_gicp.h alone of the engine's headers, names no debug hook, and its binaries need no mgicp_* symbol
+    outside that header."""
     import glob
 
     from leica_point_cloud_processing_amd import _lib
@@ -103,7 +104,10 @@ def test_drop_in_uses_the_product_header_only():
     for path in sources:
         text = open(path).read()
         assert "mi355x_gicp_debug.h" not in text, path
-        assert set(re.findall(r'#include\s*[<"]([^">]*mi355x[^">]*)[">]', text)) <= {"mi355x_gicp.h"}, path
+        # of the engine's headers the product header alone; the adapter's own headers (the shared helper
+        # context) are part of what the integrator compiles and pass through this same loop
+        own = {os.path.basename(s) for s in sources}
+        assert set(re.findall(r'#include\s*[<"]([^">]*mi355x[^">]*)[">]', text)) - own <= {"mi355x_gicp.h"}, path
         named = set(re.findall(r"\bmgicp_[a-z_0-9]+", text))
         assert not named & debug, (path, sorted(named & debug))
     subprocess.run(["make", "-s", "-C", ROOT, "adapter-example", "adapter-replay", "fod-replay"], check=True,

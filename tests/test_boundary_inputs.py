@@ -173,7 +173,7 @@ def test_neither_none_nor_all_are_boundary_points(name):
 
 def test_boundary_adapter_compiles_against_standins():
     """adapter/InitialAlignment_mi355x.cpp passes g++ -std=c++14 -Wall -Wextra -Werror against the stand-ins
-    of tests/adapter_standins_boundary and links to libmgicp.so through product symbols only."""
+    of tests/adapter_standins_ia and links to libmgicp.so through product symbols only."""
     from leica_point_cloud_processing_amd import _lib
 
     r = subprocess.run(["make", "-s", "-C", ROOT, "boundary-replay"], capture_output=True, text=True)

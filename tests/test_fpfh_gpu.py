@@ -322,7 +322,7 @@ def test_obtainFeatures_mirror():
 
 
 def test_adapter_obtainFeatures_replay(tmp_path):
-    """adapter/InitialAlignment_features_mi355x.cpp through its C++ driver: the FPFHSignature33 records of
+    """adapter/InitialAlignment_mi355x.cpp through its C++ driver: the FPFHSignature33 records of
     GICPEngine.fpfh_features at the resolution-derived radius."""
     exe = os.path.join(ROOT, "adapter", "build", "replay_test_fpfh")
     assert os.path.exists(exe), "build it with `make fpfh-replay`"

@@ -189,8 +189,8 @@ def test_histogram_reference_properties():
 
 
 def test_fpfh_adapter_compiles_against_standins():
-    """adapter/InitialAlignment_features_mi355x.cpp compiles as the catkin package would compile it, against
-    the stand-in headers of tests/adapter_standins_fpfh, and links to libmgicp.so through product symbols only."""
+    """adapter/InitialAlignment_mi355x.cpp compiles as the catkin package would compile it, against
+    the stand-in headers of tests/adapter_standins_ia, and links to libmgicp.so through product symbols only."""
     from leica_point_cloud_processing_amd import _lib
 
     r = subprocess.run(["make", "-s", "-C", ROOT, "fpfh-replay"], capture_output=True, text=True)

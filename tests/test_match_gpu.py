@@ -303,7 +303,7 @@ def test_obtainCorrespondences_mirror():
 
 
 def test_adapter_obtainCorrespondences_replay(tmp_path):
-    """adapter/InitialAlignment_correspondences_mi355x.cpp through its C++ driver: the pcl::Correspondences of
+    """adapter/InitialAlignment_mi355x.cpp through its C++ driver: the pcl::Correspondences of
     GICPEngine.match_features, compacted in ascending index_query."""
     exe = os.path.join(ROOT, "adapter", "build", "replay_test_correspondences")
     assert os.path.exists(exe), "build it with `make corr-replay`"

@@ -191,8 +191,8 @@ def test_python_binding_matches_header():
 
 
 def test_correspondences_adapter_compiles_against_standins():
-    """adapter/InitialAlignment_correspondences_mi355x.cpp compiles as the catkin package would compile it,
-    against the stand-in headers of tests/adapter_standins_corr, and links to libmgicp.so through product
+    """adapter/InitialAlignment_mi355x.cpp compiles as the catkin package would compile it,
+    against the stand-in headers of tests/adapter_standins_ia, and links to libmgicp.so through product
     symbols only."""
     from leica_point_cloud_processing_amd import _lib
 

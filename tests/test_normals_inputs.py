@@ -90,7 +90,7 @@ def test_case_shapes():
 
 
 def test_far_sheet_regimes():
-    """far_sheet: the grid's slop exceeds the radius, so a single query's cell box (fpfh_box; a group's box in
+    """far_sheet: the grid's slop exceeds the radius, so a single query's cell box (cell_box; a group's box in
     normals_tile_kernel is at least as large) has more than 64 rows of cells and more points than one staged
     chunk for at least a third of the records -- on both sides of the origin -- while the control, the same
     draws at X0 = 0, has no box above 4 x 4 rows.  Conditions on the inputs, from the float32 restatement of
