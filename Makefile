@@ -14,7 +14,7 @@ LDMAP := -Wl,--version-script=$(MAP)
 HIPFLAGS := -O3 -std=c++17 --offload-arch=$(ARCH) -fPIC -ffp-contract=off -Wall -Wno-unused-result
 
 all: $(LIB) oracle adapter-example adapter-replay fod-replay normals-replay boundary-replay fpfh-replay corr-replay \
-     harris-replay ia-replay
+     harris-replay ia-replay transform-replay
 
 OBJDIR := $(PKG)/csrc/build
 OBJS  := $(OBJDIR)/mgicp_kernels.o $(OBJDIR)/mgicp_engine.o $(OBJDIR)/mgicp_clouds.o $(OBJDIR)/mgicp_pass.o \
@@ -48,6 +48,7 @@ STANDIN     := tests/adapter_standins
 STANDIN_FOD := tests/adapter_standins_fod
 STANDIN_NRM := tests/adapter_standins_normals
 STANDIN_IA  := tests/adapter_standins_ia
+STANDIN_IAT := tests/adapter_standins_ia_transform
 define replay_rule
 adapter/build/$(2): $(3) $$(wildcard adapter/*.h) include/mi355x_gicp.h $$(foreach d,$(4),$$(wildcard $$(d)/*.h)) $(5) $$(LIB)
 	mkdir -p adapter/build
@@ -78,6 +79,11 @@ IA_REPLAYS := boundary-replay:replay_test_boundary fpfh-replay:replay_test_fpfh 
 $(foreach r,$(IA_REPLAYS),$(eval $(call replay_rule,$(word 1,$(subst :, ,$(r))),$(word 2,$(subst :, ,$(r))),\
   adapter/InitialAlignment_mi355x.cpp,$(STANDIN_IA) $(STANDIN_NRM) $(STANDIN),\
   $(STANDIN)/Utils_standin.cpp $(STANDIN_IA)/Filter_standin.cpp $(STANDIN_IA)/$(word 2,$(subst :, ,$(r))).cpp)))
+# adapter/InitialAlignment_transform_mi355x.cpp (rejectCorrespondences, rejectOneToOneCorrespondences,
+# estimateTransform): the InitialAlignment.h with the keypoint clouds, the correspondences and rigid_tf_ in
+# front; one driver that runs the three members in runKeypointsBasedAlgorithm's order on files of their inputs
+$(eval $(call replay_rule,transform-replay,replay_test_transform,adapter/InitialAlignment_transform_mi355x.cpp,\
+  $(STANDIN_IAT) $(STANDIN),$(STANDIN)/Utils_standin.cpp $(STANDIN_IAT)/replay_test_transform.cpp))
 
 oracle:
 	$(MAKE) -C oracle
@@ -86,4 +92,4 @@ clean:
 	rm -f $(LIB) $(PKG)/libmgicp_*.so $(OBJS)
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle clean adapter-example adapter-replay fod-replay normals-replay boundary-replay fpfh-replay corr-replay harris-replay ia-replay variant
+.PHONY: all oracle clean adapter-example adapter-replay fod-replay normals-replay boundary-replay fpfh-replay corr-replay harris-replay ia-replay transform-replay variant

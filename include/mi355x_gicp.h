@@ -389,6 +389,128 @@ int mgicp_match_features(mgicp_ctx* ctx,
                          size_t* n_correspondences,    /* may be NULL */
                          mgicp_match_info* info        /* may be NULL */);
 
+/* ---- the pre-alignment transform: InitialAlignment::rejectCorrespondences, rejectOneToOneCorrespondences and
+ * estimateTransform (src/InitialAlignment.cpp:519-545), the three steps after obtainCorrespondences ----
+ * PCL 1.8.1 restated [PCL]: sac.h / ransac.hpp (RandomSampleConsensus::computeModel, SampleConsensus::
+ * refineModel), sac_model.h (drawIndexSample, getSamples, computeVariance), sac_model_registration.h(pp),
+ * correspondence_rejection_sample_consensus.hpp, correspondence_rejection_one_to_one.cpp,
+ * transformation_estimation_svd.hpp and Eigen's umeyama.  PCL is not available to this project's tests, so
+ * parity with PCL binaries is unpinned (README "Parity"); the rules below are the contract, and every
+ * deviation from PCL in them is named as one.
+ * Common to the three calls: a correspondence is (index_query[i], index_match[i], distance[i]), three parallel
+ * arrays of length m (pcl::Correspondence's fields).  Keypoint clouds are x, y, z at offsets 0/4/8 of records
+ * of the given stride (>= 12, a multiple of 4; 32 = pcl::PointXYZRGB).  MGICP_E_INVALID, before any launch: an
+ * index outside its cloud, a bad pointer or stride, m or a cloud size above INT32_MAX.  Plain host pointers; no
+ * cloud slot is used: a set source / target, the helper slot and their cached state stay as they are.  The
+ * same bits in every output on every call (the info structs' times excepted).  Single rank: with a
+ * communicator attached they run locally, without a collective.
+ *
+ * Model of a set of n pairs (s_k, t_k) -- estimateRigidTransformationSVD of the registration model, umeyama
+ * without scaling, in fp64: the 15 sums  sum s (3), sum t (3), sum t_r s_c (9), each term an exact fp64 value;
+ * s_mean = sum s / n, t_mean = sum t / n, sigma_rc = (sum t_r s_c) / n - t_mean_r s_mean_c;  sigma = U D V',
+ * D descending;  S = diag(1, 1, sign(det U det V));  R = U S V';  t_r = t_mean_r - ((R_r0 s_mean_0 + R_r1
+ * s_mean_1) + R_r2 s_mean_2).  The 12 coefficients are rounded to float once (PCL's cast<float>()).
+ * Deviation (a): the sums are taken in a fixed tree that depends on n alone -- entry k of the set belongs to
+ * lane k % 64 of wave (k / 64) % 4 of block k / 256; a wave adds lanes (l, l + d) for d = 32 .. 1, a block its
+ * four waves in order, and block b's sums go to accumulator b % 256, taken in ascending b, the 256 accumulators
+ * then through the same wave-and-block tree.  Missing entries are +0.0.  (n = 3: (v0 + v2) + v1.)  PCL demeans
+ * first and adds in Eigen's order.  The SVD is a one-sided Jacobi in fp64 inside the library (Eigen uses a
+ * two-sided JacobiSVD<Matrix3d>).  A rank-deficient sigma (n < 3, collinear or coincident points) has no
+ * unique rotation: the call returns some proper rotation (det +1) and promises no more.
+ *
+ * Distance of correspondence i under a float model T (rows T_r0 .. T_r3), in float without FMA contraction:
+ * p_r = ((T_r0 x + T_r1 y) + T_r2 z) + T_r3 (mgicp_transform_source's formula), d = p - q,
+ * d2 = (dx^2 + dz^2) + dy^2 (Eigen's SSE reduction of a 4-vector whose last lane is 0: unpinned, like the
+ * rest).  Inlier iff (double)d2 < threshold * threshold, strict, the product in double as PCL takes it. */
+
+/* InitialAlignment::rejectCorrespondences (:519-530): pcl::registration::CorrespondenceRejectorSampleConsensus
+ * <PointXYZRGB> with setInlierThreshold(1.5), setRefineModel(true) and its default of 1000 iterations.
+ * Sampling (drawIndexSample, getSamples, isSampleGood): an index vector sh starts as the positions 0 .. m-1
+ * and is never reset; a draw does, for i = 0, 1, 2, swap(sh[i], sh[i + rnd() % (m - i)]) and takes
+ * sh[0 .. 2]; rnd() is boost::uniform_int<>(0, INT_MAX) over boost::mt19937 seeded with 12345: the generator's
+ * 32-bit output shifted right by one.  A draw is good iff the three pairwise squared distances of its source
+ * points, in float as ((dx^2 + dy^2) + dz^2), all satisfy (double)d > sample_dist_thresh, with
+ * sample_dist_thresh = ((sqrt(l0) + sqrt(l1) + sqrt(l2)) / 3)^2 over the singular values l_k (= the
+ * eigenvalues, never negative here) of the covariance  sum s s' / m - s_mean s_mean'  of the correspondences'
+ * source points.  Up to 1000 draws per sample; if none is good the sample is empty.  Deviation (b): that
+ * covariance comes from the fp64 sums of the tree above and the library's Jacobi; PCL computes it in float
+ * (computeMeanAndCovarianceMatrix, eigen33).  Deviation (e): PCL shuffles the index_query values and finds a
+ * sample's target through a std::map keyed by them; here positions are shuffled, which is the same thing
+ * whenever the index_query values are distinct (obtainCorrespondences' output always is).
+ * Loop (RandomSampleConsensus::computeModel, probability 0.99): iterations = 0, k = 1, best = -INT_MAX,
+ * skipped = 0; while iterations < k and skipped < 10 * max_iterations: take a sample (an empty one ends the
+ * loop); its model; count its inliers at `inlier_threshold`; a strictly larger count becomes the best and
+ * sets w = best / m, q = min(max(1 - pow(w, 3), DBL_EPSILON), 1 - DBL_EPSILON), k = log(1.0 - 0.99) / log(q);
+ * ++iterations; the loop ends when iterations > max_iterations.  (A registration model never fails on three
+ * points, so skipped stays 0; max_iterations = 0 therefore runs no iteration.)  The best model's inliers are
+ * then selected, ascending.
+ * Refine, when `refine` != 0 (SampleConsensus::refineModel(3.0, 1000)): error_threshold = inlier_threshold,
+ * prev = the selected inliers, changed = false, rounds = 0; do { the model of prev (an empty prev leaves the
+ * model as it is); note |prev|; new = the selection at error_threshold; if new is empty: ++rounds, leave when
+ * rounds >= 1000, else go to the loop condition; variance = 2.1981 * the (|new| >> 1)-th smallest (double)d2
+ * of new; error_threshold = sqrt(min(inlier_threshold^2, 9 variance)); changed = false; swap(prev, new);
+ * if |prev| != |new|: when the last four noted sizes read a, b, a, b the refine ends as "oscillating", else
+ * changed = true and go to the loop condition; otherwise changed = (prev != new) } while (changed and
+ * ++rounds < 1000).  This is the source's do-while, `continue` jumping to its condition: an empty selection
+ * in the first round therefore ends the loop (the issue text read it as "continues"; the source governs).
+ * Outcome of the refine: new empty -> failed; oscillating -> succeeded, inliers and model stay those of the
+ * loop; not changed -> succeeded, inliers = the selection, model = the last model; else (1000 rounds) failed.
+ * Outcomes of the call: keep[i] = 1 for the final inliers (PCL's remaining correspondences are those, in
+ * input order), *n_keep their number, best_T_cm the final model (column-major 4 x 4, last row 0 0 0 1).
+ * Everything kept (keep all 1, *n_keep = m) and best_T_cm = identity when m < 3, when no model was found
+ * (the first sample empty, max_iterations = 0), when the refine failed (PCL logs an error and leaves the
+ * caller's vector, which InitialAlignment passes as input and output, untouched), or when fewer than 3 final
+ * inliers remain.  MGICP_E_INVALID also for a negative or NaN inlier_threshold and max_iterations < 0.
+ * m = 0: OK.  The hypotheses are scored in batches of up to 64 on the device and PCL's sequential loop is
+ * replayed over the counts; hypotheses drawn past the loop's end change nothing, since nothing after the
+ * loop draws (DESIGN.md "Pre-alignment transform"). */
+typedef struct {
+    double n_hypotheses;          /* models scored on the device, speculative ones of the last batch included */
+    double n_iterations;          /* PCL's iterations_ when its loop ends (0 when m < 3) */
+    double n_skipped;             /* PCL's skipped_count (always 0: three points always give a model) */
+    double n_refine_rounds;       /* bodies of the refine's do-while that ran */
+    double n_inliers_ransac;      /* inliers of the best model at inlier_threshold (0: no model) */
+    double n_inliers_final;       /* inliers after the refine (= *n_keep unless everything is kept) */
+    double final_error_threshold; /* the refine's error_threshold when it ended (inlier_threshold without one) */
+    double pair_tests;            /* pair distance evaluations the device made (scoring and selections) */
+    double ms_device;             /* first launch -> stream synchronise after the last, the host's replay,
+                                     medians and 3 x 3 solves between them included */
+    double ms_total;              /* host call -> outputs written */
+} mgicp_ransac_info;
+int mgicp_reject_ransac(mgicp_ctx* ctx,
+                        const float* source_keypoints, size_t n_source, size_t source_stride_bytes,
+                        const float* target_keypoints, size_t n_target, size_t target_stride_bytes,
+                        const int* index_query, const int* index_match, size_t m,
+                        double inlier_threshold /* the reference: 1.5 */,
+                        int max_iterations /* the rejector's default: 1000 */, int refine /* the reference: 1 */,
+                        unsigned char* keep /* m */, size_t* n_keep, float best_T_cm[16],
+                        mgicp_ransac_info* info /* may be NULL */);
+
+/* InitialAlignment::rejectOneToOneCorrespondences (:532-538): pcl::registration::CorrespondenceRejectorOneToOne.
+ * For every index_match value that occurs, the survivor is the correspondence with the smallest distance;
+ * deviation (c): equal distances go to the lowest position (PCL's std::sort is unstable there).  order[0 ..
+ * *n_keep) = the survivors' positions in ascending index_match, PCL's output order; order[*n_keep .. m) = -1.
+ * index_match < 0 is skipped, as in PCL.  MGICP_E_INVALID: index_match >= n_target, a NaN or negative distance
+ * (the comparator has no defined answer for NaN), a bad pointer.  -0.0 counts as 0.  m = 0: OK. */
+int mgicp_reject_one_to_one(mgicp_ctx* ctx, const int* index_match, const float* distance, size_t m,
+                            size_t n_target, int* order /* m */, size_t* n_keep,
+                            double* ms_device /* may be NULL: first launch -> stream synchronise */);
+
+/* InitialAlignment::estimateTransform (:540-545): pcl::registration::TransformationEstimationSVD<PointXYZRGB,
+ * PointXYZRGB>::estimateRigidTransformation over the correspondences: the model above over all m pairs,
+ * T_cm column-major.  Deviation (d): PCL's Scalar is float, so its umeyama runs in float; this call reuses
+ * the fp64 path and rounds once.  m = 0: identity.  m of 1 or 2 and rank-deficient sets: the rank rule above. */
+typedef struct {
+    double sums[15];   /* sum s (3), sum t (3), sum t_r s_c (9, row-major in r), as the tree above gives them */
+    double ms_device;  /* first launch -> stream synchronise after the last */
+    double ms_total;   /* host call -> output written */
+} mgicp_svd_info;
+int mgicp_estimate_rigid_svd(mgicp_ctx* ctx,
+                             const float* source_keypoints, size_t n_source, size_t source_stride_bytes,
+                             const float* target_keypoints, size_t n_target, size_t target_stride_bytes,
+                             const int* index_query, const int* index_match, size_t m,
+                             float T_cm[16], mgicp_svd_info* info /* may be NULL */);
+
 /* ---- the FOD-side callers either side of the GICP path ----
  * pcl::SegmentDifferences<PointXYZRGB>::segment as called by Filter::removeFromCloud
  * (src/Filter.cpp:176-189) on the cloud the FSM just transformed with

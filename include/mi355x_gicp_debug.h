@@ -136,6 +136,17 @@ int mgicp_debug_vlist_layout(mgicp_ctx* ctx, double out[24], uint8_t* state, uin
  * kernel, out[5] target rows of a launch, out[6] blocks that share them and out[7] target rows of each
  * such block (the layout of the first launch); all 0 when the call ran no kernel */
 int mgicp_debug_match_stats(mgicp_ctx* ctx, long long out[8]);
+/* the scoring kernel of mgicp_reject_ransac on caller-given models: counts[b] = the correspondences whose
+ * float d2 under models_cm[b] (column-major 4 x 4, the last row ignored) satisfies (double)d2 < threshold *
+ * threshold -- the distance rule of mi355x_gicp.h "the pre-alignment transform".  n_models >= 0, any number:
+ * scored in launches of up to 64 (or the "ransac_batch" option's value).  Arguments checked as
+ * mgicp_reject_ransac checks them. */
+int mgicp_debug_score_models(mgicp_ctx* ctx,
+                             const float* source_keypoints, size_t n_source, size_t source_stride_bytes,
+                             const float* target_keypoints, size_t n_target, size_t target_stride_bytes,
+                             const int* index_query, const int* index_match, size_t m,
+                             const float* models_cm /* n_models * 16 */, int n_models, double threshold,
+                             int* counts /* n_models */);
 /* enable (1) / disable (0) per-launch HIP event timing (off by default); objective passes
  * ([2]) are sampled every 8th launch, every other family is timed on every launch */
 int mgicp_set_profiling(mgicp_ctx* ctx, int on);
@@ -146,7 +157,8 @@ int mgicp_set_profiling(mgicp_ctx* ctx, int on);
  * the default max(2^22, 32 n); 0: the default; such a context leaves no lists in the target cache),
  * "fuse_compact" (1-NN cell lists),
  * "target_cache", "match_pairs_per_launch" (mgicp_match_features: the (source, target) pairs of one launch;
- * 0: the default).  Every form gives the default path's results bit for bit (the GPU tests
+ * 0: the default), "ransac_batch" (mgicp_reject_ransac: the hypotheses of one scoring launch, 1 .. 64;
+ * 0: the default of 64).  Every form gives the default path's results bit for bit (the GPU tests
  * that pin each one: INTEGRATION.md "Debug options"); MGICP_E_INVALID for an unknown name. */
 int mgicp_debug_option(mgicp_ctx* ctx, const char* name, double value);
 /* target cache (mgicp_release_cache): out[0] the current target was adopted from the cache, out[1]

@@ -130,6 +130,29 @@ class MgicpMatchInfo(ctypes.Structure):
     ]
 
 
+class MgicpRansacInfo(ctypes.Structure):
+    _fields_ = [
+        ("n_hypotheses", ctypes.c_double),
+        ("n_iterations", ctypes.c_double),
+        ("n_skipped", ctypes.c_double),
+        ("n_refine_rounds", ctypes.c_double),
+        ("n_inliers_ransac", ctypes.c_double),
+        ("n_inliers_final", ctypes.c_double),
+        ("final_error_threshold", ctypes.c_double),
+        ("pair_tests", ctypes.c_double),
+        ("ms_device", ctypes.c_double),
+        ("ms_total", ctypes.c_double),
+    ]
+
+
+class MgicpSvdInfo(ctypes.Structure):
+    _fields_ = [
+        ("sums", ctypes.c_double * 15),
+        ("ms_device", ctypes.c_double),
+        ("ms_total", ctypes.c_double),
+    ]
+
+
 class MgicpError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"mgicp error {code}: {msg}")
@@ -169,6 +192,14 @@ _SIGNATURES = {
                                             ctypes.POINTER(MgicpFpfhInfo)]),
     "mgicp_match_features": (ctypes.c_int, [_P, _P, _SZ, _SZ, _P, _SZ, _SZ, ctypes.c_double, _P, _P,
                                              ctypes.POINTER(_SZ), ctypes.POINTER(MgicpMatchInfo)]),
+    "mgicp_reject_ransac": (ctypes.c_int, [_P, _P, _SZ, _SZ, _P, _SZ, _SZ, _P, _P, _SZ, ctypes.c_double, ctypes.c_int,
+                                            ctypes.c_int, _P, ctypes.POINTER(_SZ), _FP,
+                                            ctypes.POINTER(MgicpRansacInfo)]),
+    "mgicp_reject_one_to_one": (ctypes.c_int, [_P, _P, _P, _SZ, _SZ, _P, ctypes.POINTER(_SZ), _DP]),
+    "mgicp_estimate_rigid_svd": (ctypes.c_int, [_P, _P, _SZ, _SZ, _P, _SZ, _SZ, _P, _P, _SZ, _FP,
+                                                 ctypes.POINTER(MgicpSvdInfo)]),
+    "mgicp_debug_score_models": (ctypes.c_int, [_P, _P, _SZ, _SZ, _P, _SZ, _SZ, _P, _P, _SZ, _P, ctypes.c_int,
+                                                 ctypes.c_double, _P]),
     "mgicp_segment_differences": (ctypes.c_int, [_P, _FP, _P, _SZ, _SZ, _P, _SZ, _SZ, ctypes.c_double, _P,
                                                   ctypes.POINTER(_SZ)]),
     "mgicp_voxel_grid": (ctypes.c_int, [_P, _P, _SZ, _SZ, ctypes.c_int, _DP, ctypes.c_int, _P, _SZ,

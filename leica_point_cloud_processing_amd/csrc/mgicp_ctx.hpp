@@ -375,6 +375,8 @@ struct mgicp_ctx {
   // figures for mgicp_debug_match_stats
   unsigned long long match_pairs_per_launch = kMatchPairsPerLaunch;
   long long match_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  // mgicp_reject_ransac: hypotheses of one scoring launch (debug option "ransac_batch")
+  int ransac_batch = kRansacBatch;
   // the target's 1-NN cell lists (r04, DESIGN.md "1-NN cell lists"; debug option "vlist" 0: the r03 sweeps)
   bool vlist = true;
   bool fuse_compact = true;           // r04: compaction fused into listed sweeps (debug option "fuse_compact")

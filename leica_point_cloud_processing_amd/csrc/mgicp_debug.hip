@@ -559,6 +559,8 @@ int mgicp_debug_option(mgicp_ctx* ctx, const char* name, double value) {
   else if (n == "target_cache") ctx->tcache_on = on;    // adopt / leave the target state (process cache)
   else if (n == "match_pairs_per_launch")               // mgicp_match_features: pairs of one launch (0: the default)
     ctx->match_pairs_per_launch = value >= 1.0 ? static_cast<unsigned long long>(std::min(value, 9.0e18)) : kMatchPairsPerLaunch;
+  else if (n == "ransac_batch")                         // mgicp_reject_ransac: hypotheses of one launch (0: the default)
+    ctx->ransac_batch = iv >= 1 ? std::min(iv, kRansacBatch) : kRansacBatch;
   else if (n == "bar_cmd") {                            // server commands through the BAR (else pinned copy)
     ctx->bar = on;
     if (!on && ctx->bar_cmd) {

@@ -1,6 +1,7 @@
 // mgicp_features.hip -- the feature calls of the initial alignment (include/mi355x_gicp.h): radius normals,
-// boundary points, Harris keypoints, FPFH descriptors and feature correspondences.  Host code only: the
-// kernels and their launchers are in mgicp_kernels.hip.
+// boundary points, Harris keypoints, FPFH descriptors and feature correspondences, and the pre-alignment
+// transform after them: the RANSAC and one-to-one rejectors and the SVD estimate (their host arithmetic is
+// prealign.hpp).  Host code only: the kernels and their launchers are in mgicp_kernels.hip.
 #pragma clang fp contract(off)
 
 #include <hip/hip_runtime.h>
@@ -9,9 +10,12 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <limits>
 #include <vector>
 
+#include "../../include/mi355x_gicp_debug.h"
 #include "mgicp_ctx.hpp"
+#include "prealign.hpp"
 
 using namespace mgicp;
 
@@ -53,6 +57,82 @@ struct SlotCounters {
     for (int i = 0; i < W * Slots; ++i) sum[i % W] += slots[i];
   }
 };
+
+// ---- the pre-alignment transform: the correspondences of two keypoint clouds on the device ----
+// what the three calls refuse before any launch (mi355x_gicp.h "the pre-alignment transform")
+bool bad_pairs(const float* src, size_t ns, size_t sstride, const float* tgt, size_t nt, size_t tstride, const int* iq,
+               const int* im, size_t m) {
+  if ((ns && !src) || (nt && !tgt) || (m && (!iq || !im)) || sstride < 12 || (sstride % 4) || tstride < 12 ||
+      (tstride % 4) || ns > size_t(INT32_MAX) || nt > size_t(INT32_MAX) || m > size_t(INT32_MAX))
+    return true;
+  for (size_t i = 0; i < m; ++i)
+    if (iq[i] < 0 || static_cast<size_t>(iq[i]) >= ns || im[i] < 0 || static_cast<size_t>(im[i]) >= nt) return true;
+  return false;
+}
+
+// the packed host copies (the sampler reads them) and the device copies of the clouds and the index arrays
+struct PairSet {
+  std::vector<float> hs, ht;
+  ScopedBuf<float> d_s, d_t;
+  ScopedBuf<int> d_iq, d_im;
+  PairView view{};
+  static void pack(const float* base, size_t n, size_t stride, std::vector<float>& out) {
+    const unsigned char* p = reinterpret_cast<const unsigned char*>(base);
+    out.resize(3 * n);
+    for (size_t i = 0; i < n; ++i) std::memcpy(&out[3 * i], p + i * stride, 12);
+  }
+  // the copies read this object's vectors and the caller's arrays: the stream is synchronised before the
+  // call returns, on the error path too, so that none of them is still being read when it goes away
+  int upload(mgicp_ctx* ctx, const float* src, size_t ns, size_t sstride, const float* tgt, size_t nt, size_t tstride,
+             const int* iq, const int* im, size_t m) {
+    pack(src, ns, sstride, hs);
+    pack(tgt, nt, tstride, ht);
+    hipStream_t s = ctx->stream;
+    HIPCK(d_s.reserve(3 * ns));
+    HIPCK(d_t.reserve(3 * nt));
+    HIPCK(d_iq.reserve(m));
+    HIPCK(d_im.reserve(m));
+    hipError_t e = hipSuccess;
+    if (ns) e = hipMemcpyAsync(d_s.p, hs.data(), 3 * ns * sizeof(float), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && nt) e = hipMemcpyAsync(d_t.p, ht.data(), 3 * nt * sizeof(float), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && m) e = hipMemcpyAsync(d_iq.p, iq, m * sizeof(int), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && m) e = hipMemcpyAsync(d_im.p, im, m * sizeof(int), hipMemcpyHostToDevice, s);
+    const int rc = sync(ctx);
+    HIPCK(e);
+    if (rc) return rc;
+    view = PairView{d_s.p, d_t.p, d_iq.p, d_im.p};
+    return MGICP_OK;
+  }
+};
+
+// the 15 sums of a set of pairs, on the device and back (one synchronise)
+struct MomentBufs {
+  ScopedBuf<double> d_partial, d_out;
+  hipError_t reserve(size_t m) {
+    hipError_t e = d_partial.reserve(static_cast<size_t>(pair_moment_blocks(m)) * kRedVals);
+    return e == hipSuccess ? d_out.reserve(kRedVals) : e;
+  }
+  int run(mgicp_ctx* ctx, const PairView& v, const uint32_t* list, size_t cnt, double sums[15]) {
+    double out[kRedVals];
+    HIPCK(launch_pair_moments(v, list, cnt, d_partial.p, d_out.p, ctx->stream));
+    HIPCK(hipMemcpyAsync(out, d_out.p, sizeof(out), hipMemcpyDeviceToHost, ctx->stream));
+    int rc = sync(ctx);
+    if (rc) return rc;
+    std::copy(out, out + 15, sums);
+    return MGICP_OK;
+  }
+};
+
+void identity_cm(float T[16]) {
+  for (int i = 0; i < 16; ++i) T[i] = (i % 5 == 0) ? 1.f : 0.f;
+}
+
+// rows of a 3 x 4 -> column-major 4 x 4
+void rows_to_cm(const float T[12], float cm[16]) {
+  identity_cm(cm);
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 4; ++c) cm[4 * c + r] = T[4 * r + c];
+}
 
 }  // namespace
 
@@ -499,6 +579,329 @@ int mgicp_match_features(mgicp_ctx* ctx, const float* source, size_t n_source, s
   ctx->match_stats[6] = lay.splits;
   ctx->match_stats[7] = lay.per_split;
   return MGICP_OK;
+}
+
+int mgicp_reject_ransac(mgicp_ctx* ctx, const float* src, size_t ns, size_t sstride, const float* tgt, size_t nt,
+                        size_t tstride, const int* iq, const int* im, size_t m, double threshold, int max_iterations,
+                        int refine, unsigned char* keep, size_t* n_keep, float best_T_cm[16], mgicp_ransac_info* info) {
+  if (!ctx || !(threshold >= 0) || max_iterations < 0 || !n_keep || !best_T_cm || (m && !keep) ||
+      bad_pairs(src, ns, sstride, tgt, nt, tstride, iq, im, m))
+    return MGICP_E_INVALID;
+  HIPCK(hipSetDevice(ctx->device));
+  const double t0 = now_ms();
+  mgicp_ransac_info inf{};
+  inf.final_error_threshold = threshold;
+  // PCL's answer when it finds no model, the refine fails or fewer than 3 inliers remain: everything, identity
+  auto keep_all = [&]() {
+    if (m) std::memset(keep, 1, m);
+    *n_keep = m;
+    identity_cm(best_T_cm);
+    inf.ms_total = now_ms() - t0;
+    if (info) *info = inf;
+    return MGICP_OK;
+  };
+  if (m < 3) return keep_all();
+  hipStream_t s = ctx->stream;
+  PairSet ps;
+  MomentBufs mom;
+  ScopedBuf<float> d_models, d_d2, d_d2p;
+  ScopedBuf<unsigned int> d_counts;
+  ScopedBuf<uint32_t> d_flag, d_pos, d_list[2];
+  ScopedBuf<unsigned char> d_scratch;
+  const size_t sb = scan_scratch_bytes(m + 1);
+  int rc = ps.upload(ctx, src, ns, sstride, tgt, nt, tstride, iq, im, m);
+  if (rc) return rc;
+  HIPCK(mom.reserve(m));
+  HIPCK(d_models.reserve(kRansacBatch * 12));
+  HIPCK(d_counts.reserve(kRansacBatch));
+  HIPCK(d_d2.reserve(m));
+  HIPCK(d_d2p.reserve(m));
+  HIPCK(d_flag.reserve(m + 1));
+  HIPCK(d_pos.reserve(m + 1));
+  HIPCK(d_list[0].reserve(m));
+  HIPCK(d_list[1].reserve(m));
+  HIPCK(d_scratch.reserve(sb));
+  if ((rc = sync(ctx))) return rc;
+  const double t1 = now_ms();
+  const double md = static_cast<double>(m);
+  double pair_tests = 0.0;
+
+  // sample_dist_thresh: the covariance of the correspondences' source points, each paired with itself
+  double sums[15];
+  const PairView self{ps.view.sxyz, ps.view.sxyz, ps.view.iq, ps.view.iq};
+  if ((rc = mom.run(ctx, self, nullptr, m, sums))) return rc;
+  const double sample_thresh = prealign::sample_dist_thresh(sums, md);
+
+  // the selection of one model at one threshold: positions ascending, their (double)d2, into list buffer `buf`
+  std::vector<float> h_d2;
+  auto select = [&](const float T[12], double thr, int buf, std::vector<uint32_t>& list, std::vector<double>& d2) -> int {
+    Xf34 X;
+    std::copy(T, T + 12, X.m);
+    HIPCK(launch_ransac_select(ps.view, m, X, prealign::strict_limit(thr * thr), d_flag.p, d_pos.p, d_d2.p, d_scratch.p,
+                               sb, d_list[buf].p, d_d2p.p, s));
+    uint32_t cnt = 0;
+    HIPCK(hipMemcpyAsync(&cnt, d_pos.p + m, sizeof(cnt), hipMemcpyDeviceToHost, s));
+    int r = sync(ctx);
+    if (r) return r;
+    pair_tests += md;
+    list.resize(cnt);
+    h_d2.resize(cnt);
+    d2.resize(cnt);
+    if (cnt) {
+      HIPCK(hipMemcpyAsync(list.data(), d_list[buf].p, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+      HIPCK(hipMemcpyAsync(h_d2.data(), d_d2p.p, cnt * sizeof(float), hipMemcpyDeviceToHost, s));
+      if ((r = sync(ctx))) return r;
+    }
+    for (uint32_t k = 0; k < cnt; ++k) d2[k] = static_cast<double>(h_d2[k]);
+    return MGICP_OK;
+  };
+
+  // RandomSampleConsensus::computeModel: batches of hypotheses scored on the device, PCL's sequential loop
+  // replayed over their counts.  A batch draws on past the loop's end; nothing after the loop draws
+  prealign::Sampler sampler(m);
+  const int batch = std::max(1, std::min(ctx->ransac_batch, kRansacBatch));
+  const float lim = prealign::strict_limit(threshold * threshold);
+  const double log_probability = std::log(1.0 - 0.99);
+  const unsigned max_skip = static_cast<unsigned>(max_iterations) * 10u;
+  const unsigned skipped = 0;  // three points always give a registration model
+  int iterations = 0;
+  long long best = -static_cast<long long>(INT32_MAX);
+  double k = 1.0;
+  bool have_model = false, ended = false;
+  float best_model[12];
+  std::vector<float> models(static_cast<size_t>(kRansacBatch) * 12);
+  unsigned int counts[kRansacBatch];
+  while (!ended && iterations < k && skipped < max_skip) {
+    int nb = 0;
+    bool ran_dry = false;
+    for (; nb < batch; ++nb) {
+      int smp[3];
+      if (!sampler.sample(ps.hs.data(), iq, sample_thresh, smp)) {
+        ran_dry = true;
+        break;
+      }
+      float sp[3][3], tp[3][3];
+      for (int j = 0; j < 3; ++j) {
+        std::memcpy(sp[j], &ps.hs[3 * static_cast<size_t>(iq[smp[j]])], 12);
+        std::memcpy(tp[j], &ps.ht[3 * static_cast<size_t>(im[smp[j]])], 12);
+      }
+      double s3[15];
+      prealign::sums_of_three(sp, tp, s3);
+      prealign::model_from_sums(s3, 3.0, &models[12 * static_cast<size_t>(nb)]);
+    }
+    if (nb) {
+      HIPCK(hipMemcpyAsync(d_models.p, models.data(), static_cast<size_t>(nb) * 12 * sizeof(float), hipMemcpyHostToDevice, s));
+      HIPCK(launch_ransac_score(ps.view, m, d_models.p, nb, lim, d_counts.p, s));
+      HIPCK(hipMemcpyAsync(counts, d_counts.p, sizeof(counts), hipMemcpyDeviceToHost, s));
+      if ((rc = sync(ctx))) return rc;
+      inf.n_hypotheses += nb;
+      pair_tests += md * nb;
+    }
+    for (int j = 0; j < nb; ++j) {
+      if (!(iterations < k && skipped < max_skip)) {
+        ended = true;
+        break;
+      }
+      const long long c = counts[j];
+      if (c > best) {
+        best = c;
+        have_model = true;
+        std::copy(&models[12 * static_cast<size_t>(j)], &models[12 * static_cast<size_t>(j)] + 12, best_model);
+        const double w = static_cast<double>(best) * (1.0 / md);
+        double p_no_outliers = 1.0 - std::pow(w, 3.0);
+        p_no_outliers = std::max(std::numeric_limits<double>::epsilon(), p_no_outliers);
+        p_no_outliers = std::min(1.0 - std::numeric_limits<double>::epsilon(), p_no_outliers);
+        k = log_probability / std::log(p_no_outliers);
+      }
+      ++iterations;
+      if (iterations > max_iterations) {
+        ended = true;
+        break;
+      }
+    }
+    if (ran_dry) ended = true;  // the loop's next getSamples comes back empty
+  }
+  inf.n_iterations = iterations;
+  inf.n_skipped = skipped;
+  auto finish_times = [&]() {
+    inf.pair_tests = pair_tests;
+    inf.ms_device = now_ms() - t1;
+  };
+  if (!have_model) {
+    finish_times();
+    return keep_all();
+  }
+  std::vector<uint32_t> inliers, prev, fresh;
+  std::vector<double> d2;
+  if ((rc = select(best_model, threshold, 0, inliers, d2))) return rc;
+  inf.n_inliers_ransac = static_cast<double>(inliers.size());
+  float model[12];
+  std::copy(best_model, best_model + 12, model);
+  bool ok = true;
+  if (refine) {
+    // SampleConsensus::refineModel(3.0, 1000), statement for statement; `fresh` is PCL's new_inliers
+    const double thr2 = threshold * threshold;
+    double error_threshold = threshold;
+    unsigned rounds = 0;
+    bool changed = false, oscillating = false;
+    std::vector<size_t> sizes;
+    float cur[12];
+    std::copy(best_model, best_model + 12, cur);
+    prev = inliers;
+    int pb = 0;  // the device list buffer that holds prev
+    do {
+      inf.n_refine_rounds += 1;
+      if (!prev.empty()) {
+        if ((rc = mom.run(ctx, ps.view, d_list[pb].p, prev.size(), sums))) return rc;
+        prealign::model_from_sums(sums, static_cast<double>(prev.size()), cur);
+      }
+      sizes.push_back(prev.size());
+      if ((rc = select(cur, error_threshold, 1 - pb, fresh, d2))) return rc;
+      if (fresh.empty()) {
+        ++rounds;
+        if (rounds >= 1000) break;
+        continue;
+      }
+      const size_t mid = d2.size() >> 1;
+      std::nth_element(d2.begin(), d2.begin() + static_cast<std::ptrdiff_t>(mid), d2.end());
+      const double variance = 2.1981 * d2[mid];
+      error_threshold = std::sqrt(std::min(thr2, 9.0 * variance));
+      changed = false;
+      std::swap(prev, fresh);
+      pb = 1 - pb;
+      if (fresh.size() != prev.size()) {
+        const size_t z = sizes.size();
+        if (z >= 4 && sizes[z - 1] == sizes[z - 3] && sizes[z - 2] == sizes[z - 4]) {
+          oscillating = true;
+          break;
+        }
+        changed = true;
+        continue;
+      }
+      changed = prev != fresh;
+    } while (changed && ++rounds < 1000);
+    inf.final_error_threshold = error_threshold;
+    if (fresh.empty()) ok = false;
+    else if (oscillating) ok = true;  // inliers and model stay the loop's
+    else if (!changed) {
+      inliers.swap(fresh);
+      std::copy(cur, cur + 12, model);
+    } else ok = false;
+  }
+  finish_times();
+  inf.n_inliers_final = ok ? static_cast<double>(inliers.size()) : 0.0;
+  if (!ok || inliers.size() < 3) return keep_all();
+  std::memset(keep, 0, m);
+  for (uint32_t p : inliers) keep[p] = 1;
+  *n_keep = inliers.size();
+  rows_to_cm(model, best_T_cm);
+  inf.ms_total = now_ms() - t0;
+  if (info) *info = inf;
+  return MGICP_OK;
+}
+
+int mgicp_reject_one_to_one(mgicp_ctx* ctx, const int* im, const float* distance, size_t m, size_t nt, int* order,
+                            size_t* n_keep, double* ms_device) {
+  if (!ctx || !n_keep || (m && (!im || !distance || !order)) || m > size_t(INT32_MAX) || nt > size_t(INT32_MAX))
+    return MGICP_E_INVALID;
+  std::vector<float> hd(m);
+  for (size_t i = 0; i < m; ++i) {
+    if ((im[i] >= 0 && static_cast<size_t>(im[i]) >= nt) || !(distance[i] >= 0.f)) return MGICP_E_INVALID;
+    hd[i] = distance[i] == 0.f ? 0.f : distance[i];  // -0.0 orders as 0
+  }
+  HIPCK(hipSetDevice(ctx->device));
+  *n_keep = 0;
+  if (ms_device) *ms_device = 0.0;
+  if (m == 0) return MGICP_OK;
+  hipStream_t s = ctx->stream;
+  ScopedBuf<int> d_im, d_order;
+  ScopedBuf<float> d_dist;
+  ScopedBuf<unsigned long long> d_best;
+  ScopedBuf<uint32_t> d_flag, d_pos;
+  ScopedBuf<unsigned char> d_scratch;
+  const size_t sb = scan_scratch_bytes(nt + 1);
+  HIPCK(d_im.reserve(m));
+  HIPCK(d_order.reserve(m));
+  HIPCK(d_dist.reserve(m));
+  HIPCK(d_best.reserve(std::max<size_t>(nt, 1)));
+  HIPCK(d_flag.reserve(nt + 1));
+  HIPCK(d_pos.reserve(nt + 1));
+  HIPCK(d_scratch.reserve(sb));
+  HIPCK(hipMemcpyAsync(d_im.p, im, m * sizeof(int), hipMemcpyHostToDevice, s));
+  HIPCK(hipMemcpyAsync(d_dist.p, hd.data(), m * sizeof(float), hipMemcpyHostToDevice, s));
+  int rc = sync(ctx);
+  if (rc) return rc;
+  const double t1 = now_ms();
+  HIPCK(launch_one_to_one(d_im.p, d_dist.p, m, nt, d_best.p, d_flag.p, d_pos.p, d_scratch.p, sb, d_order.p, s));
+  if ((rc = sync(ctx))) return rc;
+  if (ms_device) *ms_device = now_ms() - t1;
+  uint32_t cnt = 0;
+  HIPCK(hipMemcpyAsync(order, d_order.p, m * sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCK(hipMemcpyAsync(&cnt, d_pos.p + nt, sizeof(cnt), hipMemcpyDeviceToHost, s));
+  if ((rc = sync(ctx))) return rc;
+  *n_keep = cnt;
+  return MGICP_OK;
+}
+
+int mgicp_estimate_rigid_svd(mgicp_ctx* ctx, const float* src, size_t ns, size_t sstride, const float* tgt, size_t nt,
+                             size_t tstride, const int* iq, const int* im, size_t m, float T_cm[16],
+                             mgicp_svd_info* info) {
+  if (!ctx || !T_cm || bad_pairs(src, ns, sstride, tgt, nt, tstride, iq, im, m)) return MGICP_E_INVALID;
+  HIPCK(hipSetDevice(ctx->device));
+  const double t0 = now_ms();
+  mgicp_svd_info inf{};
+  identity_cm(T_cm);
+  if (info) *info = inf;
+  if (m == 0) return MGICP_OK;
+  PairSet ps;
+  MomentBufs mom;
+  int rc = ps.upload(ctx, src, ns, sstride, tgt, nt, tstride, iq, im, m);
+  if (rc) return rc;
+  HIPCK(mom.reserve(m));
+  if ((rc = sync(ctx))) return rc;
+  const double t1 = now_ms();
+  if ((rc = mom.run(ctx, ps.view, nullptr, m, inf.sums))) return rc;
+  inf.ms_device = now_ms() - t1;
+  float T[12];
+  prealign::model_from_sums(inf.sums, static_cast<double>(m), T);
+  rows_to_cm(T, T_cm);
+  inf.ms_total = now_ms() - t0;
+  if (info) *info = inf;
+  return MGICP_OK;
+}
+
+int mgicp_debug_score_models(mgicp_ctx* ctx, const float* src, size_t ns, size_t sstride, const float* tgt, size_t nt,
+                             size_t tstride, const int* iq, const int* im, size_t m, const float* models_cm,
+                             int n_models, double threshold, int* counts) {
+  if (!ctx || !(threshold >= 0) || n_models < 0 || (n_models && (!models_cm || !counts)) ||
+      bad_pairs(src, ns, sstride, tgt, nt, tstride, iq, im, m))
+    return MGICP_E_INVALID;
+  HIPCK(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  PairSet ps;
+  ScopedBuf<float> d_models;
+  ScopedBuf<unsigned int> d_counts;
+  int rc = ps.upload(ctx, src, ns, sstride, tgt, nt, tstride, iq, im, m);
+  if (rc) return rc;
+  HIPCK(d_models.reserve(kRansacBatch * 12));
+  HIPCK(d_counts.reserve(kRansacBatch));
+  const int batch = std::max(1, std::min(ctx->ransac_batch, kRansacBatch));
+  const float lim = prealign::strict_limit(threshold * threshold);
+  std::vector<float> rows(static_cast<size_t>(kRansacBatch) * 12);
+  unsigned int got[kRansacBatch];
+  for (int b0 = 0; b0 < n_models; b0 += batch) {
+    const int nb = std::min(batch, n_models - b0);
+    for (int b = 0; b < nb; ++b) {
+      const Xf34 x = Mat4::from_cm(models_cm + 16 * static_cast<size_t>(b0 + b)).xf();
+      std::copy(x.m, x.m + 12, &rows[12 * static_cast<size_t>(b)]);
+    }
+    HIPCK(hipMemcpyAsync(d_models.p, rows.data(), static_cast<size_t>(nb) * 12 * sizeof(float), hipMemcpyHostToDevice, s));
+    HIPCK(launch_ransac_score(ps.view, m, d_models.p, nb, lim, d_counts.p, s));
+    HIPCK(hipMemcpyAsync(got, d_counts.p, sizeof(got), hipMemcpyDeviceToHost, s));
+    if ((rc = sync(ctx))) return rc;
+    for (int b = 0; b < nb; ++b) counts[b0 + b] = static_cast<int>(got[b]);
+  }
+  return sync(ctx);
 }
 
 }  // extern "C"

@@ -429,6 +429,36 @@ hipError_t launch_match(const float* src, size_t ns, const float* tgt, size_t t_
                         unsigned long long* running, unsigned long long* partial, unsigned long long* ctr,
                         hipStream_t s);
 
+// The rejectors and the SVD estimate of the pre-alignment (InitialAlignment::rejectCorrespondences,
+// rejectOneToOneCorrespondences, estimateTransform) over m correspondences (iq[i], im[i]) between two
+// keypoint clouds held as packed xyz; the caller has checked every index against its cloud.
+struct PairView {
+  const float* sxyz;  // 3 floats per source record
+  const float* txyz;  // 3 floats per target record
+  const int* iq;      // m source record indices
+  const int* im;      // m target record indices
+};
+constexpr int kRansacBatch = 64;  // models of one scoring launch
+// score: counts[b] (kRansacBatch words, zeroed here) = correspondences with float d2 < lim under model b of
+// the nb (<= kRansacBatch) models, 12 floats each (the rows of a 3 x 4).  select: flag / pos (m + 1 words),
+// d2 (m); the inliers' positions ascending in list and their d2 in d2_packed, their number in pos[m].
+// moments: the 15 sums of pair_moments_kernel over list[0 .. cnt) (nullptr: 0 .. cnt) into out[16];
+// partial: pair_moment_blocks(cnt) * kRedVals doubles.
+hipError_t launch_ransac_score(const PairView& v, size_t m, const float* models, int nb, float lim,
+                               unsigned int* counts, hipStream_t s);
+hipError_t launch_ransac_select(const PairView& v, size_t m, Xf34 T, float lim, uint32_t* flag, uint32_t* pos,
+                                float* d2, void* scratch, size_t scratch_bytes, uint32_t* list, float* d2_packed,
+                                hipStream_t s);
+int        pair_moment_blocks(size_t cnt);
+hipError_t launch_pair_moments(const PairView& v, const uint32_t* list, size_t cnt, double* partial, double* out,
+                               hipStream_t s);
+// one-to-one: order[0 .. pos[nt]) = per target with a correspondence, ascending, the position of its
+// smallest (dist, position); the rest of order[m] = -1.  im[i] < 0 is skipped, every other im[i] < nt;
+// dist non-negative, no NaN, no -0.  best: max(nt, 1) words; flag / pos: nt + 1; scratch for nt + 1
+hipError_t launch_one_to_one(const int* im, const float* dist, size_t m, size_t nt, unsigned long long* best,
+                             uint32_t* flag, uint32_t* pos, void* scratch, size_t scratch_bytes, int* order,
+                             hipStream_t s);
+
 #if defined(MGICP_CORR_PHASES) && MGICP_CORR_PHASES
 hipError_t corr_phase_take(unsigned long long out[24]);  // diagnostic builds: read and reset
 #endif

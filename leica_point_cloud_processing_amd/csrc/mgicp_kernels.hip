@@ -5501,6 +5501,166 @@ hipError_t launch_reduce_finish(const double* partial, int nb, double* out, hipS
   return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------
+// pre-alignment transform: the rejectors and the SVD estimate (DESIGN.md "Pre-alignment transform")
+// ------------------------------------------------------------------------------------
+// correspondence i's two points: packed xyz of its source and target records
+__device__ __forceinline__ void pair_points(const PairView& v, uint32_t i, float (&s)[3], float (&q)[3]) {
+  const float* a = v.sxyz + 3 * static_cast<size_t>(v.iq[i]);
+  const float* b = v.txyz + 3 * static_cast<size_t>(v.im[i]);
+  s[0] = a[0], s[1] = a[1], s[2] = a[2];
+  q[0] = b[0], q[1] = b[1], q[2] = b[2];
+}
+
+// squared distance of a pair under a 3 x 4 float model: xform's sums, then (dx^2 + dz^2) + dy^2 (Eigen's
+// packet reduction of a 4-vector whose last lane is 0); the file is compiled without FMA contraction
+__device__ __forceinline__ float pair_d2(const float* T, const float (&s)[3], const float (&q)[3]) {
+  const float px = ((T[0] * s[0] + T[1] * s[1]) + T[2] * s[2]) + T[3];
+  const float py = ((T[4] * s[0] + T[5] * s[1]) + T[6] * s[2]) + T[7];
+  const float pz = ((T[8] * s[0] + T[9] * s[1]) + T[10] * s[2]) + T[11];
+  const float dx = px - q[0], dy = py - q[1], dz = pz - q[2];
+  return (dx * dx + dz * dz) + dy * dy;
+}
+
+// hypothesis scoring: a lane per correspondence holds its two points in registers and walks the nb models
+// of the batch, which sit in LDS and are read through wave-uniform addresses.  Per model a wave's votes are
+// one ballot, a block's one LDS counter, and a block adds one integer to counts[b]: integer sums have no
+// order, so the counts are the same bits in every run.  d2 < lim is (double)d2 < thr^2 (prealign::strict_limit)
+__global__ __launch_bounds__(256) void ransac_score_kernel(PairView v, uint32_t m, const float* __restrict__ models,
+                                                           int nb, float lim, unsigned int* __restrict__ counts) {
+  __shared__ float sm[kRansacBatch * 12];
+  __shared__ unsigned int cnt[kRansacBatch];
+  for (int k = threadIdx.x; k < nb * 12; k += 256) sm[k] = models[k];
+  if (threadIdx.x < static_cast<unsigned>(nb)) cnt[threadIdx.x] = 0;
+  __syncthreads();
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  const bool live = i < m;
+  float s[3] = {0.f, 0.f, 0.f}, q[3] = {0.f, 0.f, 0.f};
+  if (live) pair_points(v, i, s, q);
+  for (int b = 0; b < nb; ++b) {
+    const float d2 = pair_d2(sm + 12 * b, s, q);
+    const unsigned long long votes = __ballot(live && d2 < lim);
+    if ((threadIdx.x & 63) == 0 && votes) atomicAdd(&cnt[b], static_cast<unsigned int>(__popcll(votes)));
+  }
+  __syncthreads();
+  if (threadIdx.x < static_cast<unsigned>(nb) && cnt[threadIdx.x]) atomicAdd(&counts[threadIdx.x], cnt[threadIdx.x]);
+}
+
+// select: one model; flag[i] = inlier (flag[m] = 0 closes the scan), d2[i] its squared distance
+__global__ void ransac_select_kernel(PairView v, uint32_t m, Xf34 T, float lim, uint32_t* __restrict__ flag,
+                                     float* __restrict__ d2) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i > m) return;
+  if (i == m) {
+    flag[m] = 0;
+    return;
+  }
+  float s[3], q[3];
+  pair_points(v, i, s, q);
+  const float d = pair_d2(T.m, s, q);
+  d2[i] = d;
+  flag[i] = d < lim ? 1u : 0u;
+}
+
+// the flagged positions, ascending, and their d2 packed beside them
+__global__ void ransac_scatter_kernel(const uint32_t* __restrict__ flag, const uint32_t* __restrict__ pos, uint32_t m,
+                                      const float* __restrict__ d2, uint32_t* __restrict__ list,
+                                      float* __restrict__ d2_packed) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m || !flag[i]) return;
+  list[pos[i]] = i;
+  d2_packed[pos[i]] = d2[i];
+}
+
+// the 15 sums of a point set's model: [0..2] sum s, [3..5] sum t, [6 + 3 r + c] sum t_r s_c, each term an
+// exact fp64 product of two floats.  Entry k of the set (list[k], or k without a list) belongs to thread
+// k % 256 of block k / 256; block_reduce_store's tree, then reduce_finish_kernel over the blocks: the tree
+// depends on cnt alone
+__global__ __launch_bounds__(256) void pair_moments_kernel(PairView v, const uint32_t* __restrict__ list, uint32_t cnt,
+                                                           double* __restrict__ partial) {
+  double acc[kRedVals];
+#pragma unroll
+  for (int k = 0; k < kRedVals; ++k) acc[k] = 0.0;
+  const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+  if (k < cnt) {
+    float s[3], q[3];
+    pair_points(v, list ? list[k] : k, s, q);
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      acc[r] = static_cast<double>(s[r]);
+      acc[3 + r] = static_cast<double>(q[r]);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) acc[6 + 3 * r + c] = static_cast<double>(q[r]) * static_cast<double>(s[c]);
+    }
+  }
+  block_reduce_store(acc, partial + static_cast<size_t>(blockIdx.x) * kRedVals);
+}
+
+// one-to-one: per target the smallest (distance bits << 32) | position among its correspondences
+// (non-negative floats order as their bits do; equal distances go to the lowest position)
+__global__ void o2o_min_kernel(const int* __restrict__ im, const float* __restrict__ dist, uint32_t m,
+                               unsigned long long* __restrict__ best) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m || im[i] < 0) return;
+  atomicMin(&best[im[i]], (static_cast<unsigned long long>(__float_as_uint(dist[i])) << 32) | i);
+}
+
+__global__ void o2o_flag_kernel(const unsigned long long* __restrict__ best, uint32_t nt, uint32_t* __restrict__ flag) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t > nt) return;
+  flag[t] = (t < nt && best[t] != ~0ull) ? 1u : 0u;
+}
+
+__global__ void o2o_scatter_kernel(const unsigned long long* __restrict__ best, const uint32_t* __restrict__ flag,
+                                   const uint32_t* __restrict__ pos, uint32_t nt, int* __restrict__ order) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < nt && flag[t]) order[pos[t]] = static_cast<int>(static_cast<uint32_t>(best[t]));
+}
+
+hipError_t launch_ransac_score(const PairView& v, size_t m, const float* models, int nb, float lim,
+                               unsigned int* counts, hipStream_t s) {
+  hipError_t e = hipMemsetAsync(counts, 0, kRansacBatch * sizeof(unsigned int), s);
+  if (e != hipSuccess || !m || nb < 1) return e;
+  ransac_score_kernel<<<nblk(m), 256, 0, s>>>(v, static_cast<uint32_t>(m), models, std::min(nb, kRansacBatch), lim, counts);
+  return hipGetLastError();
+}
+
+hipError_t launch_ransac_select(const PairView& v, size_t m, Xf34 T, float lim, uint32_t* flag, uint32_t* pos,
+                                float* d2, void* scratch, size_t scratch_bytes, uint32_t* list, float* d2_packed,
+                                hipStream_t s) {
+  ransac_select_kernel<<<nblk(m + 1), 256, 0, s>>>(v, static_cast<uint32_t>(m), T, lim, flag, d2);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  if ((e = launch_exclusive_scan(scratch, scratch_bytes, flag, pos, m + 1, s)) != hipSuccess || !m) return e;
+  ransac_scatter_kernel<<<nblk(m), 256, 0, s>>>(flag, pos, static_cast<uint32_t>(m), d2, list, d2_packed);
+  return hipGetLastError();
+}
+
+int pair_moment_blocks(size_t cnt) { return static_cast<int>(nblk(std::max<size_t>(cnt, 1))); }
+
+hipError_t launch_pair_moments(const PairView& v, const uint32_t* list, size_t cnt, double* partial, double* out,
+                               hipStream_t s) {
+  const int nb = pair_moment_blocks(cnt);
+  pair_moments_kernel<<<nb, 256, 0, s>>>(v, list, static_cast<uint32_t>(cnt), partial);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  return launch_reduce_finish(partial, nb, out, s);
+}
+
+hipError_t launch_one_to_one(const int* im, const float* dist, size_t m, size_t nt, unsigned long long* best,
+                             uint32_t* flag, uint32_t* pos, void* scratch, size_t scratch_bytes, int* order,
+                             hipStream_t s) {
+  hipError_t e = hipMemsetAsync(best, 0xff, std::max<size_t>(nt, 1) * sizeof(unsigned long long), s);
+  if (e == hipSuccess && m) e = hipMemsetAsync(order, 0xff, m * sizeof(int), s);
+  if (e != hipSuccess) return e;
+  if (m) o2o_min_kernel<<<nblk(m), 256, 0, s>>>(im, dist, static_cast<uint32_t>(m), best);
+  o2o_flag_kernel<<<nblk(nt + 1), 256, 0, s>>>(best, static_cast<uint32_t>(nt), flag);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  if ((e = launch_exclusive_scan(scratch, scratch_bytes, flag, pos, nt + 1, s)) != hipSuccess || !nt || !m) return e;
+  o2o_scatter_kernel<<<nblk(nt), 256, 0, s>>>(best, flag, pos, static_cast<uint32_t>(nt), order);
+  return hipGetLastError();
+}
+
 hipError_t launch_finite_compact(const float4* in, size_t n, uint32_t* flags, uint32_t* pos,
                                  void* scratch, size_t scratch_bytes, float4* out, hipStream_t s) {
   finite_flags_kernel<<<nblk(n + 1), 256, 0, s>>>(in, n, flags);
@@ -5916,6 +6076,13 @@ hipError_t preload_kernels(void* pinned, size_t pinned_bytes, hipStream_t s) {
       reinterpret_cast<const void*>(&harris_nms_wave_kernel),
       reinterpret_cast<const void*>(&match_kernel),
       reinterpret_cast<const void*>(&match_merge_kernel),
+      reinterpret_cast<const void*>(&ransac_score_kernel),
+      reinterpret_cast<const void*>(&ransac_select_kernel),
+      reinterpret_cast<const void*>(&ransac_scatter_kernel),
+      reinterpret_cast<const void*>(&pair_moments_kernel),
+      reinterpret_cast<const void*>(&o2o_min_kernel),
+      reinterpret_cast<const void*>(&o2o_flag_kernel),
+      reinterpret_cast<const void*>(&o2o_scatter_kernel),
   };
   for (const void* f : fns) {
     hipFuncAttributes attr;

@@ -389,6 +389,94 @@ class GICPEngine:
         info = {f: getattr(mi, f) for f, _ in mi._fields_}
         return match[:ns], dist[:ns], info
 
+    # -- the pre-alignment transform: the rejectors and the SVD estimate -------------------------
+    @staticmethod
+    def _keypoint_arg(cloud):
+        """(owner, pointer or None, n, stride) of a keypoint cloud: a PointCloudRGB, or float32 rows of at least
+        3 values whose first 3 are x, y, z (passed with their stride)"""
+        if isinstance(cloud, PointCloudRGB):
+            _p, n, stride = cloud.ctypes_xyz()
+            return cloud, ctypes.c_void_p(_p) if n else None, n, stride
+        a = np.asarray(cloud)
+        if a.ndim != 2 or a.shape[1] < 3:
+            a = a.reshape(-1, 3)
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        return a, ctypes.c_void_p(a.ctypes.data) if len(a) else None, len(a), 4 * a.shape[1]
+
+    @staticmethod
+    def _index_arg(idx, m=None):
+        a = np.ascontiguousarray(idx, dtype=np.int32).reshape(-1)
+        if m is not None and len(a) != m:
+            raise ValueError(f"the correspondence arrays differ in length: {len(a)} and {m}")
+        return a
+
+    def _pair_args(self, source_keypoints, target_keypoints, index_query, index_match):
+        sk, sp, ns, ss = self._keypoint_arg(source_keypoints)
+        tk, tp, nt, ts = self._keypoint_arg(target_keypoints)
+        iq = self._index_arg(index_query)
+        im = self._index_arg(index_match, len(iq))
+        m = len(iq)
+        return (sk, tk, iq, im), (sp, ns, ss, tp, nt, ts, ctypes.c_void_p(iq.ctypes.data) if m else None,
+                                  ctypes.c_void_p(im.ctypes.data) if m else None, m)
+
+    def reject_ransac(self, source_keypoints, target_keypoints, index_query, index_match,
+                      inlier_threshold: float = 1.5, max_iterations: int = 1000, refine: bool = True):
+        """pcl::registration::CorrespondenceRejectorSampleConsensus (InitialAlignment::rejectCorrespondences):
+        (keep bool[m], best_T float32[4, 4], info).  The remaining correspondences are those with keep, in
+        input order; everything is kept and best_T is the identity when PCL returns its input (no model, a
+        failed refine, fewer than 3 inliers)."""
+        _alive, args = self._pair_args(source_keypoints, target_keypoints, index_query, index_match)
+        m = args[-1]
+        keep = np.zeros(max(m, 1), np.uint8)
+        cnt = ctypes.c_size_t()
+        T = np.zeros(16, np.float32)
+        ri = _lib.MgicpRansacInfo()
+        self._check(self._lib.mgicp_reject_ransac(self._h, *args, float(inlier_threshold), int(max_iterations),
+                                                  int(bool(refine)), keep.ctypes.data, ctypes.byref(cnt), _fp(T),
+                                                  ctypes.byref(ri)), "reject_ransac")
+        info = {f: getattr(ri, f) for f, _ in ri._fields_}
+        info["n_keep"] = int(cnt.value)
+        return keep[:m].astype(bool), _from_cm(T), info
+
+    def reject_one_to_one(self, index_match, distance, n_target: int):
+        """pcl::registration::CorrespondenceRejectorOneToOne (InitialAlignment::rejectOneToOneCorrespondences):
+        (order int32[n_keep], info) -- the positions of the surviving correspondences in ascending index_match:
+        per target the smallest distance, equal distances the lowest position."""
+        im = self._index_arg(index_match)
+        m = len(im)
+        d = np.ascontiguousarray(distance, dtype=np.float32).reshape(-1)
+        if len(d) != m:
+            raise ValueError(f"the correspondence arrays differ in length: {len(d)} and {m}")
+        order = np.full(max(m, 1), -1, np.int32)
+        cnt = ctypes.c_size_t()
+        ms = ctypes.c_double()
+        self._check(self._lib.mgicp_reject_one_to_one(
+            self._h, ctypes.c_void_p(im.ctypes.data) if m else None, ctypes.c_void_p(d.ctypes.data) if m else None, m,
+            int(n_target), order.ctypes.data, ctypes.byref(cnt), ctypes.byref(ms)), "reject_one_to_one")
+        assert (order[int(cnt.value):m] == -1).all()
+        return order[:int(cnt.value)].copy(), {"n_keep": int(cnt.value), "ms_device": ms.value}
+
+    def estimate_rigid_svd(self, source_keypoints, target_keypoints, index_query, index_match):
+        """pcl::registration::TransformationEstimationSVD (InitialAlignment::estimateTransform) over the
+        correspondences: (T float32[4, 4], info); info["sums"] are the 15 raw fp64 sums."""
+        _alive, args = self._pair_args(source_keypoints, target_keypoints, index_query, index_match)
+        T = np.zeros(16, np.float32)
+        si = _lib.MgicpSvdInfo()
+        self._check(self._lib.mgicp_estimate_rigid_svd(self._h, *args, _fp(T), ctypes.byref(si)), "estimate_rigid_svd")
+        return _from_cm(T), {"sums": np.array(si.sums[:], np.float64), "ms_device": si.ms_device,
+                             "ms_total": si.ms_total}
+
+    def debug_score_models(self, source_keypoints, target_keypoints, index_query, index_match, models, threshold):
+        """mgicp_debug_score_models: the inlier count of each [4, 4] model in `models` ([B, 4, 4])"""
+        _alive, args = self._pair_args(source_keypoints, target_keypoints, index_query, index_match)
+        mod = np.asarray(models, dtype=np.float32).reshape(-1, 4, 4)
+        cm = np.ascontiguousarray(mod.transpose(0, 2, 1)).reshape(-1)
+        counts = np.zeros(max(len(mod), 1), np.int32)
+        self._check(self._lib.mgicp_debug_score_models(
+            self._h, *args, ctypes.c_void_p(cm.ctypes.data) if len(mod) else None, len(mod), float(threshold),
+            counts.ctypes.data), "debug_score_models")
+        return counts[:len(mod)]
+
     # -- FOD-side callers (SURVEY.md 8f rows 2 and 4) ------------------------------------------
     def segment_differences(self, cloud_in, cloud_sub, sqr_threshold: float, T=None):
         """pcl::SegmentDifferences (Filter::removeFromCloud): bool keep mask over cloud_in (after T)

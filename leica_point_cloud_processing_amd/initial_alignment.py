@@ -1,12 +1,12 @@
 """InitialAlignment -- the pre-alignment's steps that run on the MI355X engine.
 
-Four members of the reference class (src/InitialAlignment.cpp): obtainBoundaryKeypoints, the keypoint step
+Seven members of the reference class (src/InitialAlignment.cpp): obtainBoundaryKeypoints, the keypoint step
 of the BOUNDARY (default) and NORMALS methods, obtainHarrisKeypoints, the keypoint step of HARRIS,
-obtainFeatures, the FPFH descriptors at the keypoints (BOUNDARY and HARRIS), and obtainCorrespondences, the
-nearest target descriptor of every source descriptor.  BOUNDARY and HARRIS thus run on the engine from the
-normals to the correspondences.  The normals they take come from gicp_alignment.getNormals
-(Utils::getNormals).  Only the rejectors (rejectCorrespondences, rejectOneToOneCorrespondences) and
-estimateTransform remain off the engine.
+obtainFeatures, the FPFH descriptors at the keypoints (BOUNDARY and HARRIS), obtainCorrespondences, the
+nearest target descriptor of every source descriptor, and the three steps that turn the correspondences
+into rigid_tf_: rejectCorrespondences (RANSAC), rejectOneToOneCorrespondences and estimateTransform (SVD).
+runKeypointsBasedAlgorithm chains them as the reference does, so BOUNDARY and HARRIS run on the engine from
+the normals to the transform.  The normals they take come from gicp_alignment.getNormals (Utils::getNormals).
 """
 from __future__ import annotations
 
@@ -19,6 +19,8 @@ BOUNDARY_K_SEARCH = 30             # detector.setKSearch(30)
 BOUNDARY_ANGLE_THRESHOLD = 1.047   # detector.setAngleThreshold(1.047f)
 RADIUS_FACTOR = 1.4                # radius_factor_ (the constructor's default)
 HARRIS_THRESHOLD = np.float32(1e-6)  # detector.setThreshold(1e-6): PCL's threshold_ is a float
+RANSAC_INLIER_THRESHOLD = 1.5      # rejector.setInlierThreshold(1.5)
+RANSAC_MAX_ITERATIONS = 1000       # CorrespondenceRejectorSampleConsensus's default max_iterations_
 
 
 def obtainBoundaryKeypoints(cloud, normals, engine: GICPEngine | None = None):
@@ -99,3 +101,89 @@ def obtainCorrespondences(source_features, target_features, engine: GICPEngine |
     match, distance, _info = engine.match_features(source_features, target_features)
     index_query = np.flatnonzero(match >= 0).astype(np.int32)
     return index_query, match[index_query], distance[index_query]
+
+
+def _xyz(cloud):
+    return cloud.xyz() if isinstance(cloud, PointCloudRGB) else np.asarray(cloud, np.float32).reshape(-1, 3)
+
+
+def rejectCorrespondences(source_keypoints, target_keypoints, correspondences, engine: GICPEngine | None = None):
+    """InitialAlignment::rejectCorrespondences (src/InitialAlignment.cpp:519-530):
+    pcl::registration::CorrespondenceRejectorSampleConsensus with an inlier threshold of 1.5, refinement and the
+    rejector's 1000 iterations.  `correspondences` is obtainCorrespondences' triple; returns the remaining
+    triple, in input order (all of it when PCL finds no model or the refinement fails)."""
+    if engine is None:
+        from .filter import _engine
+
+        engine = _engine()
+    iq, im, dist = (np.asarray(a) for a in correspondences)
+    if len(iq) == 0:  # getCorrespondences leaves an empty input alone
+        return iq, im, dist
+    keep, _T, _info = engine.reject_ransac(source_keypoints, target_keypoints, iq, im, RANSAC_INLIER_THRESHOLD,
+                                           RANSAC_MAX_ITERATIONS, True)
+    return iq[keep], im[keep], dist[keep]
+
+
+def rejectOneToOneCorrespondences(correspondences, n_target: int, engine: GICPEngine | None = None):
+    """InitialAlignment::rejectOneToOneCorrespondences (src/InitialAlignment.cpp:532-538):
+    pcl::registration::CorrespondenceRejectorOneToOne.  n_target bounds index_match (the target keypoints'
+    number).  Returns the surviving triple in ascending index_match."""
+    if engine is None:
+        from .filter import _engine
+
+        engine = _engine()
+    iq, im, dist = (np.asarray(a) for a in correspondences)
+    if len(iq) == 0:
+        return iq, im, dist
+    order, _info = engine.reject_one_to_one(im, dist, n_target)
+    return iq[order], im[order], dist[order]
+
+
+def estimateTransform(source_keypoints, target_keypoints, correspondences, engine: GICPEngine | None = None):
+    """InitialAlignment::estimateTransform (src/InitialAlignment.cpp:540-545):
+    pcl::registration::TransformationEstimationSVD over the correspondences.  Returns (rigid_tf float32[4, 4],
+    transform_exists): the reference sets transform_exists_ when rigid_tf_ is not the zero matrix."""
+    if engine is None:
+        from .filter import _engine
+
+        engine = _engine()
+    iq, im, _dist = correspondences
+    T, _info = engine.estimate_rigid_svd(source_keypoints, target_keypoints, iq, im)
+    return T, bool(np.any(T != 0))
+
+
+def runKeypointsBasedAlgorithm(source, target, method: str = "BOUNDARY", radius_factor: float = RADIUS_FACTOR,
+                               engine: GICPEngine | None = None):
+    """InitialAlignment::runKeypointsBasedAlgorithm (src/InitialAlignment.cpp:117-128) for the BOUNDARY and
+    HARRIS methods: keypoints and features of both clouds, obtainCorrespondences, rejectCorrespondences,
+    rejectOneToOneCorrespondences when more than source_cloud.size() / 2 (integer division) correspondences
+    remain, estimateTransform.  `source` and `target` are (cloud, normals) pairs (normals: getNormals' array).
+    Returns (rigid_tf float32[4, 4], transform_exists, steps): steps holds every intermediate result."""
+    if method not in ("BOUNDARY", "HARRIS"):
+        raise ValueError(f"method must be BOUNDARY or HARRIS, got {method!r}")
+    if engine is None:
+        from .filter import _engine
+
+        engine = _engine()
+    steps = {}
+    for name, (cloud, normals) in (("source", source), ("target", target)):
+        if method == "BOUNDARY":
+            _status, kp, _non = obtainBoundaryKeypoints(cloud, normals, engine)
+        else:
+            _status, kp = obtainHarrisKeypoints(cloud, normals, radius_factor, engine)
+        _status, features = obtainFeatures(cloud, normals, kp, radius_factor, engine)
+        steps[name + "_keypoints_indices"] = kp
+        steps[name + "_keypoints"] = np.ascontiguousarray(_xyz(cloud)[kp], np.float32)
+        steps[name + "_features"] = features
+    sk, tk = steps["source_keypoints"], steps["target_keypoints"]
+    corr = obtainCorrespondences(steps["source_features"], steps["target_features"], engine)
+    steps["correspondences"] = corr
+    corr = rejectCorrespondences(sk, tk, corr, engine)
+    steps["correspondences_ransac"] = corr
+    source_size = source[0].size() if isinstance(source[0], PointCloudRGB) else len(_xyz(source[0]))
+    steps["one_to_one"] = len(corr[0]) > source_size // 2
+    if steps["one_to_one"]:
+        corr = rejectOneToOneCorrespondences(corr, len(tk), engine)
+    steps["correspondences_final"] = corr
+    T, exists = estimateTransform(sk, tk, corr, engine)
+    return T, exists, steps
