@@ -14,7 +14,7 @@ LDMAP := -Wl,--version-script=$(MAP)
 HIPFLAGS := -O3 -std=c++17 --offload-arch=$(ARCH) -fPIC -ffp-contract=off -Wall -Wno-unused-result
 
 all: $(LIB) oracle adapter-example adapter-replay fod-replay normals-replay boundary-replay fpfh-replay corr-replay \
-     harris-replay ia-replay transform-replay
+     harris-replay ia-replay transform-replay normals-cluster-replay
 
 OBJDIR := $(PKG)/csrc/build
 OBJS  := $(OBJDIR)/mgicp_kernels.o $(OBJDIR)/mgicp_engine.o $(OBJDIR)/mgicp_clouds.o $(OBJDIR)/mgicp_pass.o \
@@ -49,6 +49,7 @@ STANDIN_FOD := tests/adapter_standins_fod
 STANDIN_NRM := tests/adapter_standins_normals
 STANDIN_IA  := tests/adapter_standins_ia
 STANDIN_IAT := tests/adapter_standins_ia_transform
+STANDIN_IAN := tests/adapter_standins_ia_normals
 define replay_rule
 adapter/build/$(2): $(3) $$(wildcard adapter/*.h) include/mi355x_gicp.h $$(foreach d,$(4),$$(wildcard $$(d)/*.h)) $(5) $$(LIB)
 	mkdir -p adapter/build
@@ -84,6 +85,11 @@ $(foreach r,$(IA_REPLAYS),$(eval $(call replay_rule,$(word 1,$(subst :, ,$(r))),
 # front; one driver that runs the three members in runKeypointsBasedAlgorithm's order on files of their inputs
 $(eval $(call replay_rule,transform-replay,replay_test_transform,adapter/InitialAlignment_transform_mi355x.cpp,\
   $(STANDIN_IAT) $(STANDIN),$(STANDIN)/Utils_standin.cpp $(STANDIN_IAT)/replay_test_transform.cpp))
+# adapter/InitialAlignment_normals_mi355x.cpp (obtainNormalsCluster, obtainDominantNormals): the
+# InitialAlignment.h with pcl::PointIndices in front, then the Utils.h with pcl::Normal; one driver that runs the
+# two members in runNormalsBasedAlgorithm's order on files of their inputs
+$(eval $(call replay_rule,normals-cluster-replay,replay_test_normals_cluster,adapter/InitialAlignment_normals_mi355x.cpp,\
+  $(STANDIN_IAN) $(STANDIN_NRM) $(STANDIN),$(STANDIN)/Utils_standin.cpp $(STANDIN_IAN)/replay_test_normals_cluster.cpp))
 
 oracle:
 	$(MAKE) -C oracle
@@ -92,4 +98,4 @@ clean:
 	rm -f $(LIB) $(PKG)/libmgicp_*.so $(OBJS)
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle clean adapter-example adapter-replay fod-replay normals-replay boundary-replay fpfh-replay corr-replay harris-replay ia-replay transform-replay variant
+.PHONY: all oracle clean adapter-example adapter-replay fod-replay normals-replay boundary-replay fpfh-replay corr-replay harris-replay ia-replay transform-replay normals-cluster-replay variant

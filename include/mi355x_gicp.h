@@ -511,6 +511,75 @@ int mgicp_estimate_rigid_svd(mgicp_ctx* ctx,
                              const int* index_query, const int* index_match, size_t m,
                              float T_cm[16], mgicp_svd_info* info /* may be NULL */);
 
+/* ---- the NORMALS method's own steps: normal clustering and the dominant normals ----
+ * InitialAlignment::obtainNormalsCluster (:130-161): pcl::extractEuclideanClusters(cloud, normals, 0.05f, tree,
+ * clusters, 20 degrees, 2.5 % of n), the free function's overload with normals, PCL 1.8.1
+ * segmentation/extract_clusters.h restated [PCL] (unpinned against PCL binaries, like every feature call).
+ * Link: records i != j are linked iff both are finite and FLANN's float ((dx^2 + dy^2) + dz^2) <
+ * float(tolerance * tolerance), strict: the predicate of mgicp_euclidean_clusters and mgicp_radius_filter.
+ * Compatible with seed s: d = ((n_s.x n_j.x + n_s.y n_j.y) + n_s.z n_j.z) in float without FMA contraction
+ * (PCL multiplies floats and widens the sum); j is compatible iff fabs(acos((double)d)) < eps_angle.  PCL
+ * compares with the normal of the cluster's SEED (normals.points[i]), not with the normal of the point being
+ * expanded.  A NaN d, or d > 1.0f, gives acos = NaN and is not compatible: about 5 % of float-normalised unit
+ * vectors have a float self-dot of 1.0000001, and a face whose normals are all bit-identical to such a vector
+ * comes out as singletons.  That is PCL's behaviour and is kept.
+ * Rounds: `processed` starts false for every finite record; rounds run in ascending s over the unprocessed
+ * finite records.  The seed is in its cluster whatever its own normal is.  C_s = the records reachable from s
+ * by links through records that were unprocessed at the start of the round and are compatible with s.  All of
+ * C_s becomes processed whether or not it is reported: a cluster that is too small still consumes its points,
+ * and processed points are never traversed again -- they block the paths of later rounds.  So the result is
+ * not a partition by a symmetric predicate: it depends on the seed order and on what earlier rounds consumed.
+ * Output: C_s is reported iff max(min_size, 1) <= |C_s| <= max_size (max_size = 0: no cap).  Clusters come in
+ * ascending seed (= ascending smallest member; the free function does not sort by size), members ascending.
+ * labels / indices / offsets as mgicp_euclidean_clusters.
+ * Deviations: (1) non-finite records belong to no round and link to nothing (PCL asserts; the FOD helpers'
+ * convention).  (2) PCL skips nn_indices[0] as "the query itself"; with exact duplicates FLANN may put the
+ * duplicate first.  Here the link is the predicate above, self excluded, and duplicates link.  (3) libm's acos
+ * enters only on the host, once per call: c_min = the smallest float f with acos((double)f) < eps_angle,
+ * found by stepping with nextafterf from float(cos(eps_angle)) (20 degrees: 0.9396927f); the device tests
+ * d >= c_min && d <= 1.0f.  eps_angle = 0: nothing is compatible; eps_angle > pi: every d in [-1, 1] is.
+ * tolerance or eps_angle negative or NaN, bad pointers or strides: MGICP_E_INVALID.  n = 0: no cluster.
+ * float(tolerance^2) = 0 links nothing.  The rounds run on the device: small rounds consecutively in one
+ * workgroup, a round that outgrows it level by level over the whole device (DESIGN.md "Normal clustering");
+ * a round's set is a closure, so neither the split nor the order of claims changes it.
+ * Uses the helper cloud slot: a set source / target and their cached state stay as they are.  The same bits
+ * in every output on every call (the info struct's times excepted).  Single rank: with a communicator
+ * attached it runs locally, without a collective. */
+typedef struct {
+    double n_rounds;           /* rounds = seeds, singletons and unreported clusters included */
+    double n_clusters;         /* reported clusters */
+    double n_clustered_points; /* records in reported clusters */
+    double n_levels;           /* frontier launches of the level-synchronous path */
+    double n_wide_rounds;      /* rounds that left the one-workgroup path */
+    double pair_tests;         /* candidate records the expansions walked (each one's processed word is read;
+                                  distance and normal are evaluated for the unprocessed ones) */
+    double ms_grid;            /* host call -> grid of the finite records built, normals uploaded */
+    double ms_device;          /* first launch -> stream synchronise after the member sort, the per-level
+                                  read-backs between them included */
+    double ms_total;           /* host call -> outputs written */
+} mgicp_normal_cluster_info;
+int mgicp_normal_clusters(mgicp_ctx* ctx, const float* xyz, size_t n, size_t stride_bytes,
+                          const float* normals /* 3 floats per record */, size_t normal_stride_bytes,
+                          double tolerance /* the reference: 0.05f */, double eps_angle /* 20 * (M_PI / 180) */,
+                          size_t min_size /* (int)n * 0.025 */, size_t max_size /* 0: no cap */,
+                          int* labels /* n */, int* indices /* n */, size_t* offsets /* n + 1 */,
+                          mgicp_normal_cluster_info* info /* may be NULL */);
+
+/* InitialAlignment::obtainDominantNormals (:163-187): per cluster c = indices[offsets[c] .. offsets[c + 1]) the
+ * sum of the members' normals PLUS THE FIRST MEMBER'S ONCE MORE (the reference starts its accumulator at
+ * member 0 and then adds every member), normalised as Eigen's normalize() does: divided by the norm when the
+ * squared norm is > 0, else left as it is.  out[3 c ..] = that vector.  A NaN member gives a NaN normal, as in
+ * the reference.  Deviation: the sums are fp64, in the fixed tree of the "Model" rule above taken per
+ * cluster over its size + 1 entries (entry 0 = the first member, entry 1 + i = member i), which depends on the
+ * cluster's size alone; norm = sqrt((x^2 + y^2) + z^2) and the quotients in fp64, rounded to float once.  The
+ * reference adds Vector4f's in member order in float.  An empty cluster, an index outside [0, n), bad
+ * pointers or strides: MGICP_E_INVALID.  n_clusters = 0: OK.  One segmented launch pair serves every cluster.
+ * No cloud slot is used. */
+int mgicp_dominant_normals(mgicp_ctx* ctx, const float* normals, size_t n, size_t normal_stride_bytes,
+                           const int* indices, const size_t* offsets /* n_clusters + 1 */, size_t n_clusters,
+                           float* out /* n_clusters * 3 */,
+                           double* ms_device /* may be NULL: first launch -> result on the host */);
+
 /* ---- the FOD-side callers either side of the GICP path ----
  * pcl::SegmentDifferences<PointXYZRGB>::segment as called by Filter::removeFromCloud
  * (src/Filter.cpp:176-189) on the cloud the FSM just transformed with

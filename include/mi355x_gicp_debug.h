@@ -158,7 +158,9 @@ int mgicp_set_profiling(mgicp_ctx* ctx, int on);
  * "fuse_compact" (1-NN cell lists),
  * "target_cache", "match_pairs_per_launch" (mgicp_match_features: the (source, target) pairs of one launch;
  * 0: the default), "ransac_batch" (mgicp_reject_ransac: the hypotheses of one scoring launch, 1 .. 64;
- * 0: the default of 64).  Every form gives the default path's results bit for bit (the GPU tests
+ * 0: the default of 64), "nc_small_limit" (mgicp_normal_clusters: the records above which a round leaves the
+ * one-workgroup path for the level-synchronous one, 1 .. 4096; 1: every multi-record round; 0: the default of
+ * 256).  Every form gives the default path's results bit for bit (the GPU tests
  * that pin each one: INTEGRATION.md "Debug options"); MGICP_E_INVALID for an unknown name. */
 int mgicp_debug_option(mgicp_ctx* ctx, const char* name, double value);
 /* target cache (mgicp_release_cache): out[0] the current target was adopted from the cache, out[1]

@@ -153,6 +153,20 @@ class MgicpSvdInfo(ctypes.Structure):
     ]
 
 
+class MgicpNormalClusterInfo(ctypes.Structure):
+    _fields_ = [
+        ("n_rounds", ctypes.c_double),
+        ("n_clusters", ctypes.c_double),
+        ("n_clustered_points", ctypes.c_double),
+        ("n_levels", ctypes.c_double),
+        ("n_wide_rounds", ctypes.c_double),
+        ("pair_tests", ctypes.c_double),
+        ("ms_grid", ctypes.c_double),
+        ("ms_device", ctypes.c_double),
+        ("ms_total", ctypes.c_double),
+    ]
+
+
 class MgicpError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"mgicp error {code}: {msg}")
@@ -198,6 +212,9 @@ _SIGNATURES = {
     "mgicp_reject_one_to_one": (ctypes.c_int, [_P, _P, _P, _SZ, _SZ, _P, ctypes.POINTER(_SZ), _DP]),
     "mgicp_estimate_rigid_svd": (ctypes.c_int, [_P, _P, _SZ, _SZ, _P, _SZ, _SZ, _P, _P, _SZ, _FP,
                                                  ctypes.POINTER(MgicpSvdInfo)]),
+    "mgicp_normal_clusters": (ctypes.c_int, [_P, _P, _SZ, _SZ, _P, _SZ, ctypes.c_double, ctypes.c_double, _SZ, _SZ, _P, _P,
+                                              _P, ctypes.POINTER(MgicpNormalClusterInfo)]),
+    "mgicp_dominant_normals": (ctypes.c_int, [_P, _P, _SZ, _SZ, _P, _P, _SZ, _P, _DP]),
     "mgicp_debug_score_models": (ctypes.c_int, [_P, _P, _SZ, _SZ, _P, _SZ, _SZ, _P, _P, _SZ, _P, ctypes.c_int,
                                                  ctypes.c_double, _P]),
     "mgicp_segment_differences": (ctypes.c_int, [_P, _FP, _P, _SZ, _SZ, _P, _SZ, _SZ, ctypes.c_double, _P,

@@ -377,6 +377,8 @@ struct mgicp_ctx {
   long long match_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   // mgicp_reject_ransac: hypotheses of one scoring launch (debug option "ransac_batch")
   int ransac_batch = kRansacBatch;
+  // mgicp_normal_clusters: records above which a round goes wide (debug option "nc_small_limit")
+  int nc_small_limit = static_cast<int>(kNcSmallLimit);
   // the target's 1-NN cell lists (r04, DESIGN.md "1-NN cell lists"; debug option "vlist" 0: the r03 sweeps)
   bool vlist = true;
   bool fuse_compact = true;           // r04: compaction fused into listed sweeps (debug option "fuse_compact")

@@ -561,6 +561,8 @@ int mgicp_debug_option(mgicp_ctx* ctx, const char* name, double value) {
     ctx->match_pairs_per_launch = value >= 1.0 ? static_cast<unsigned long long>(std::min(value, 9.0e18)) : kMatchPairsPerLaunch;
   else if (n == "ransac_batch")                         // mgicp_reject_ransac: hypotheses of one launch (0: the default)
     ctx->ransac_batch = iv >= 1 ? std::min(iv, kRansacBatch) : kRansacBatch;
+  else if (n == "nc_small_limit")                       // mgicp_normal_clusters: records above which a round goes wide (0: the default)
+    ctx->nc_small_limit = iv >= 1 ? std::min(iv, static_cast<int>(kNcSmallCap)) : static_cast<int>(kNcSmallLimit);
   else if (n == "bar_cmd") {                            // server commands through the BAR (else pinned copy)
     ctx->bar = on;
     if (!on && ctx->bar_cmd) {

@@ -1,7 +1,7 @@
 // mgicp_features.hip -- the feature calls of the initial alignment (include/mi355x_gicp.h): radius normals,
 // boundary points, Harris keypoints, FPFH descriptors and feature correspondences, and the pre-alignment
 // transform after them: the RANSAC and one-to-one rejectors and the SVD estimate (their host arithmetic is
-// prealign.hpp).  Host code only: the kernels and their launchers are in mgicp_kernels.hip.
+// prealign.hpp); and the NORMALS method's own steps, normal clustering and the dominant normals.  Host code only: the kernels and their launchers are in mgicp_kernels.hip.
 #pragma clang fp contract(off)
 
 #include <hip/hip_runtime.h>
@@ -57,6 +57,18 @@ struct SlotCounters {
     for (int i = 0; i < W * Slots; ++i) sum[i % W] += slots[i];
   }
 };
+
+// Normal clustering's angle test without acos on the device: the smallest float f with
+// acos((double)f) < eps_angle by this host's libm, found by stepping from float(cos(eps_angle)); the device
+// tests d >= c_min && d <= 1.  Nothing is compatible at eps_angle <= 0 (+inf); above pi every d in [-1, 1] is.
+float normal_cluster_c_min(double eps_angle) {
+  if (!(eps_angle > 0)) return std::numeric_limits<float>::infinity();
+  if (eps_angle > M_PI) return -1.0f;
+  float f = std::min(1.0f, std::max(-1.0f, static_cast<float>(std::cos(eps_angle))));
+  while (f > -1.0f && std::acos(static_cast<double>(std::nextafterf(f, -2.0f))) < eps_angle) f = std::nextafterf(f, -2.0f);
+  while (f <= 1.0f && !(std::acos(static_cast<double>(f)) < eps_angle)) f = std::nextafterf(f, 2.0f);
+  return f;
+}
 
 // ---- the pre-alignment transform: the correspondences of two keypoint clouds on the device ----
 // what the three calls refuse before any launch (mi355x_gicp.h "the pre-alignment transform")
@@ -867,6 +879,192 @@ int mgicp_estimate_rigid_svd(mgicp_ctx* ctx, const float* src, size_t ns, size_t
   rows_to_cm(T, T_cm);
   inf.ms_total = now_ms() - t0;
   if (info) *info = inf;
+  return MGICP_OK;
+}
+
+int mgicp_normal_clusters(mgicp_ctx* ctx, const float* xyz, size_t n, size_t stride, const float* normals,
+                          size_t normal_stride, double tolerance, double eps_angle, size_t min_size, size_t max_size,
+                          int* labels, int* indices, size_t* offsets, mgicp_normal_cluster_info* info) {
+  if (!ctx || !(tolerance >= 0) || !(eps_angle >= 0) || !offsets || (n && (!xyz || !normals || !labels || !indices)) ||
+      stride < 12 || (stride % 4) || normal_stride < 12 || (normal_stride % 4) || n > size_t(INT32_MAX))
+    return MGICP_E_INVALID;
+  HIPCK(hipSetDevice(ctx->device));
+  const double t0 = now_ms();
+  mgicp_normal_cluster_info inf{};
+  if (info) *info = inf;
+  offsets[0] = 0;
+  if (n == 0) return MGICP_OK;
+  const FlannRadius fr(tolerance);
+  const float r2 = fr.r2;
+  // the forced tolerance / 2 grid of the Euclidean clustering (the walks are exact for any edge)
+  int rc = aux_grid(ctx, xyz, n, stride, r2 > 0.f ? std::min(0.5 * fr.reach, 1e30) : 0.0);
+  if (rc) return rc;
+  std::fill(labels, labels + n, -1);
+  std::fill(offsets, offsets + n + 1, size_t(0));
+  const size_t nf = ctx->aux.n;
+  if (nf == 0) return MGICP_OK;
+  const float c_min = normal_cluster_c_min(eps_angle);
+  const GridView& g = ctx->aux.view;
+  hipStream_t s = ctx->stream;
+  int bits = 1;
+  while ((size_t(1) << bits) < n && bits < 32) ++bits;
+  const size_t sb = sort_scratch_bytes(nf, bits);
+  PackedNormals nrm(normals, n, normal_stride);
+  ScopedBuf<float4> d_nrm;
+  ScopedBuf<uint32_t> d_owner, d_order, d_front[2];
+  ScopedBuf<unsigned int> d_count;
+  ScopedBuf<NcState> d_state;
+  SlotCounters<1, kNcCtrSlots> ctr;
+  HIPCK(nrm.reserve());
+  HIPCK(d_nrm.reserve(nf));
+  HIPCK(d_owner.reserve(nf));
+  HIPCK(d_order.reserve(nf));
+  HIPCK(d_front[0].reserve(nf));
+  HIPCK(d_front[1].reserve(nf));
+  HIPCK(d_count.reserve(2));
+  HIPCK(d_state.reserve(1));
+  HIPCK(ctr.reserve());
+  HIPCK(ctx->cc_members.reserve(nf));
+  HIPCK(ctx->keys.reserve(nf));
+  HIPCK(ctx->keys_sorted.reserve(nf));
+  HIPCK(ctx->vals.reserve(nf));
+  HIPCK(ctx->scratch.reserve(sb));
+  HIPCK(nrm.upload(s));
+  if ((rc = sync(ctx))) return rc;
+  const double t1 = now_ms();
+  HIPCK(hipMemsetAsync(d_state.p, 0, sizeof(NcState), s));
+  HIPCK(hipMemsetAsync(d_count.p, 0, 2 * sizeof(unsigned int), s));
+  HIPCK(ctr.zero(s));
+  HIPCK(launch_nc_begin(g, ctx->aux.perm.p, nf, nrm.dev.p, d_nrm.p, d_owner.p, d_order.p, s));
+  // small path until a round hands over, that round's levels on the wide path, and again: at most nf
+  // rounds and nf levels in all, as every one of them claims a record
+  const uint32_t limit = static_cast<uint32_t>(ctx->nc_small_limit);
+  NcState st{};
+  size_t levels = 0, wide_rounds = 0;
+  for (size_t turn = 0; turn <= nf; ++turn) {
+    HIPCK(launch_nc_small(g, nf, d_nrm.p, d_order.p, d_owner.p, r2, c_min, limit, d_front[0].p, d_state.p, s));
+    HIPCK(hipMemcpyAsync(&st, d_state.p, sizeof(st), hipMemcpyDeviceToHost, s));
+    if ((rc = sync(ctx))) return rc;
+    if (st.status == 0) break;
+    ++wide_rounds;
+    const float* sn = &nrm.host[3 * static_cast<size_t>(st.seed)];
+    // a level: one launch and the read-back of its count through the pinned scratch.  Both counters are zero
+    // here: a round ends on a zero count, and its last launch zeroed the other one
+    unsigned int cnt = st.count;
+    int cur = 0;
+    while (cnt && levels <= nf) {
+      if (cnt > nf) return fail(ctx, MGICP_E_HIP, "normal clusters: a frontier larger than the cloud");
+      HIPCK(launch_nc_expand(g, d_nrm.p, d_owner.p, d_front[cur].p, cnt, r2, sn, c_min, st.seed, d_front[1 - cur].p,
+                             d_count.p, cur, ctr.dev.p, s));
+      HIPCK(hipMemcpyAsync(ctx->h_small, d_count.p + cur, sizeof(cnt), hipMemcpyDeviceToHost, s));
+      if ((rc = sync(ctx))) return rc;
+      std::memcpy(&cnt, ctx->h_small, sizeof(cnt));
+      ++levels;
+      cur = 1 - cur;
+    }
+  }
+  if (st.status != 0) return fail(ctx, MGICP_E_HIP, "normal clusters: the rounds did not end");
+  HIPCK(launch_nc_emit(g, ctx->aux.perm.p, nf, d_owner.p, ctx->keys.p, ctx->vals.p, s));
+  HIPCK(launch_sort_pairs(ctx->scratch.p, sb, ctx->keys.p, ctx->keys_sorted.p, ctx->vals.p, ctx->cc_members.p, nf, bits, s));
+  if ((rc = sync(ctx))) return rc;
+  const double t2 = now_ms();
+  std::vector<uint32_t> hk(nf), hv(nf);
+  HIPCK(hipMemcpyAsync(hk.data(), ctx->keys_sorted.p, nf * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  HIPCK(hipMemcpyAsync(hv.data(), ctx->cc_members.p, nf * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  HIPCK(ctr.fetch(s));
+  if ((rc = sync(ctx))) return rc;
+  ctr.add_up();
+  // runs of equal seeds come in ascending seed, PCL's output order (the free function does not sort by size)
+  const size_t lo = std::max<size_t>(min_size, 1), hi = max_size ? max_size : SIZE_MAX;
+  size_t off = 0, nc = 0, rounds = 0;
+  for (size_t i = 0; i < nf;) {
+    size_t j = i + 1;
+    while (j < nf && hk[j] == hk[i]) ++j;
+    ++rounds;
+    if (j - i >= lo && j - i <= hi) {
+      offsets[nc] = off;
+      for (size_t m = i; m < j; ++m) {
+        indices[off++] = static_cast<int>(hv[m]);
+        labels[hv[m]] = static_cast<int>(nc);
+      }
+      ++nc;
+    }
+    i = j;
+  }
+  for (size_t c = nc; c <= n; ++c) offsets[c] = off;
+  if (rounds != st.rounds) return fail(ctx, MGICP_E_HIP, "normal clusters: the rounds run and the sets found disagree");
+  inf.n_rounds = static_cast<double>(rounds);
+  inf.n_clusters = static_cast<double>(nc);
+  inf.n_clustered_points = static_cast<double>(off);
+  inf.n_levels = static_cast<double>(levels);
+  inf.n_wide_rounds = static_cast<double>(wide_rounds);
+  inf.pair_tests = static_cast<double>(ctr.sum[0] + st.walked);
+  inf.ms_grid = t1 - t0;
+  inf.ms_device = t2 - t1;
+  inf.ms_total = now_ms() - t0;
+  if (info) *info = inf;
+  return MGICP_OK;
+}
+
+int mgicp_dominant_normals(mgicp_ctx* ctx, const float* normals, size_t n, size_t normal_stride, const int* indices,
+                           const size_t* offsets, size_t n_clusters, float* out, double* ms_device) {
+  if (!ctx || (n && !normals) || normal_stride < 12 || (normal_stride % 4) || n > size_t(INT32_MAX) ||
+      n_clusters > size_t(INT32_MAX) || (n_clusters && (!indices || !offsets || !out)))
+    return MGICP_E_INVALID;
+  if (ms_device) *ms_device = 0.0;
+  if (n_clusters == 0) return MGICP_OK;
+  // every cluster non-empty, every member a record; the blocks of 256 entries (size + 1 of them per cluster)
+  std::vector<uint32_t> blk_first(n_clusters + 1), blk_cluster;
+  std::vector<unsigned long long> off64(n_clusters + 1);
+  for (size_t c = 0; c < n_clusters; ++c) {
+    if (offsets[c + 1] <= offsets[c]) return fail(ctx, MGICP_E_INVALID, "dominant normals: an empty cluster");
+    const size_t nb = (offsets[c + 1] - offsets[c] + 1 + 255) / 256;
+    if (blk_cluster.size() + nb > size_t(INT32_MAX)) return MGICP_E_INVALID;
+    blk_first[c] = static_cast<uint32_t>(blk_cluster.size());
+    blk_cluster.insert(blk_cluster.end(), nb, static_cast<uint32_t>(c));
+    off64[c] = offsets[c] - offsets[0];
+  }
+  blk_first[n_clusters] = static_cast<uint32_t>(blk_cluster.size());
+  const size_t total = offsets[n_clusters] - offsets[0];
+  off64[n_clusters] = total;
+  const int* idx = indices + offsets[0];
+  for (size_t i = 0; i < total; ++i)
+    if (idx[i] < 0 || static_cast<size_t>(idx[i]) >= n)
+      return fail(ctx, MGICP_E_INVALID, "dominant normals: member index outside [0, n)");
+  HIPCK(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  PackedNormals nrm(normals, n, normal_stride);
+  ScopedBuf<int> d_idx;
+  ScopedBuf<unsigned long long> d_off;
+  ScopedBuf<uint32_t> d_bc, d_bf;
+  ScopedBuf<double> d_partial;
+  ScopedBuf<float> d_out;
+  std::vector<float> ho(3 * n_clusters);
+  HIPCK(nrm.reserve());
+  HIPCK(d_idx.reserve(total));
+  HIPCK(d_off.reserve(n_clusters + 1));
+  HIPCK(d_bc.reserve(blk_cluster.size()));
+  HIPCK(d_bf.reserve(n_clusters + 1));
+  HIPCK(d_partial.reserve(blk_cluster.size() * kRedVals));
+  HIPCK(d_out.reserve(3 * n_clusters));
+  // the copies read this call's vectors: the stream is synchronised before any of them goes away
+  hipError_t e = nrm.upload(s);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_idx.p, idx, total * sizeof(int), hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_off.p, off64.data(), off64.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_bc.p, blk_cluster.data(), blk_cluster.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_bf.p, blk_first.data(), blk_first.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s);
+  int rc = sync(ctx);
+  HIPCK(e);
+  if (rc) return rc;
+  const double t1 = now_ms();
+  e = launch_dominant_normals(nrm.dev.p, d_idx.p, d_off.p, d_bc.p, d_bf.p, blk_cluster.size(), n_clusters, d_partial.p,
+                              d_out.p, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(ho.data(), d_out.p, ho.size() * sizeof(float), hipMemcpyDeviceToHost, s);
+  rc = sync(ctx);
+  HIPCK(e);
+  if (rc) return rc;
+  if (ms_device) *ms_device = now_ms() - t1;
+  std::copy(ho.begin(), ho.end(), out);
   return MGICP_OK;
 }
 

@@ -459,6 +459,39 @@ hipError_t launch_one_to_one(const int* im, const float* dist, size_t m, size_t 
                              uint32_t* flag, uint32_t* pos, void* scratch, size_t scratch_bytes, int* order,
                              hipStream_t s);
 
+// Normal clustering (InitialAlignment::obtainNormalsCluster) over a grid of n finite points: PCL's serial
+// rounds, each the closure of its seed.  begin: owner[n] = free, order[rank in original order] = sorted
+// position, the normals (3 floats per original record) packed into nrm (n, grid order).  small: one
+// workgroup runs consecutive rounds from state->cursor until the cursor passes n or a round holds more than
+// `limit` (1 .. kNcSmallCap) records after a level; that round's frontier is then spill[0 .. state->count)
+// and expand continues it, one launch per level: frontier[0 .. count) -> next / counts[parity]; counts (two
+// words, both zero when a round's first level is launched) alternate: a launch zeroes counts[parity ^ 1].
+// ctr (kNcCtrSlots words, zeroed by the caller) += candidates walked by expand; small adds its own to the
+// state.  emit: (owner, original index) at each record's rank in original order, for the stable sort.
+struct NcState {
+  uint32_t cursor, status, seed, seed_pos, count, rounds;
+  unsigned long long walked;
+};
+constexpr uint32_t kNcSmallCap = 4096;   // records of a round the small path can hold (its LDS frontiers)
+constexpr uint32_t kNcSmallLimit = 256;  // records above which a round goes wide (debug option "nc_small_limit")
+constexpr int kNcCtrSlots = 256;
+hipError_t launch_nc_begin(const GridView& g, const uint32_t* perm, size_t n, const float* normals, float4* nrm,
+                           uint32_t* owner, uint32_t* order, hipStream_t s);
+hipError_t launch_nc_small(const GridView& g, size_t n, const float4* nrm, const uint32_t* order, uint32_t* owner,
+                           float r2, float c_min, uint32_t limit, uint32_t* spill, NcState* state, hipStream_t s);
+hipError_t launch_nc_expand(const GridView& g, const float4* nrm, uint32_t* owner, const uint32_t* frontier,
+                            uint32_t count, float r2, const float seed_normal[3], float c_min, uint32_t seed,
+                            uint32_t* next, unsigned int* counts, int parity, unsigned long long* ctr, hipStream_t s);
+hipError_t launch_nc_emit(const GridView& g, const uint32_t* perm, size_t n, const uint32_t* owner, uint32_t* keys,
+                          uint32_t* vals, hipStream_t s);
+// Dominant normals (InitialAlignment::obtainDominantNormals): out[3 c] = the normalised fp64 sum of cluster
+// c's entries (its first member, then every member) in the tree of launch_pair_moments taken per cluster.
+// blk_cluster[n_blocks]: the cluster of every block of 256 entries; blk_first[n_clusters + 1]: a cluster's
+// first block; partial: n_blocks * kRedVals doubles.
+hipError_t launch_dominant_normals(const float* normals, const int* indices, const unsigned long long* offsets,
+                                   const uint32_t* blk_cluster, const uint32_t* blk_first, size_t n_blocks,
+                                   size_t n_clusters, double* partial, float* out, hipStream_t s);
+
 #if defined(MGICP_CORR_PHASES) && MGICP_CORR_PHASES
 hipError_t corr_phase_take(unsigned long long out[24]);  // diagnostic builds: read and reset
 #endif

@@ -5965,6 +5965,303 @@ hipError_t launch_cc_labels(const GridView& g, const uint32_t* perm, size_t n, u
   return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------
+// Normal clustering (pcl::extractEuclideanClusters with normals, as InitialAlignment::obtainNormalsCluster
+// calls it): serial rounds in ascending seed, each the closure of its seed under "linked, unprocessed and
+// compatible with the SEED's normal" (include/mi355x_gicp.h has the rule, DESIGN.md "Normal clustering"
+// the argument).
+// ------------------------------------------------------------------------------------
+// owner[] (by sorted position) is kNcFree until a round claims the record, then the round's seed (an
+// original index) for good: a word only ever changes once, free -> seed, by an atomicCAS.  A round's set is
+// a closure, so which wave claims a record cannot change it; only the order inside a frontier can differ.
+// Expansion is level-synchronous: a launch (wide path) or a turn between two barriers (small path) expands
+// one frontier, each of its records by one wave that walks the record's cell box with lanes over the rows'
+// positions; winners of the CAS go to the next frontier with one atomic add per 64 candidates.  No wave
+// waits for another.  Every read of owner[] is a relaxed agent-scope atomic load: a plain load may be
+// served from a cache line fetched before another wave's claim, and the cursor must not take a claimed
+// record for a seed.
+constexpr uint32_t kNcFree = 0xffffffffu;
+
+__device__ __forceinline__ uint32_t nc_owner(const uint32_t* owner, uint32_t j) {
+  return __hip_atomic_load(owner + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// Does this lane claim candidate j for the round of `seed`, whose normal is sn?  q is the record being
+// expanded (itself owned already, so never a candidate).  d in float without contraction, PCL's order;
+// NaN and d > 1 are not compatible (PCL's acos gives NaN there).
+__device__ __forceinline__ bool nc_try(const GridView& g, const float4* __restrict__ nrm, uint32_t* owner, uint32_t j,
+                                       const float4& q, float r2, const float4& sn, float c_min, uint32_t seed) {
+  if (nc_owner(owner, j) != kNcFree) return false;
+  if (!(dist2(q.x, q.y, q.z, g.pts[j]) < r2)) return false;
+  const float4 m = nrm[j];
+  const float d = (sn.x * m.x + sn.y * m.y) + sn.z * m.z;
+  if (!(d >= c_min && d <= 1.0f)) return false;
+  return atomicCAS(owner + j, kNcFree, seed) == kNcFree;
+}
+
+// One wave expands the record at sorted position p -- the rows row_first, row_first + row_step, ... of its
+// box, so that the waves of a workgroup can share a record; put(slot, j) stores winner j at `slot` of the
+// next frontier, whose counter is `count` (global or LDS).  Returns the candidates walked (one per wave).
+template <class Put>
+__device__ __forceinline__ unsigned long long nc_expand_one(const GridView& g, const float4* __restrict__ nrm,
+                                                            uint32_t* owner, uint32_t p, float r2, const float4& sn,
+                                                            float c_min, uint32_t seed, unsigned int* count, int lane,
+                                                            int row_first, int row_step, Put&& put) {
+  const float4 q = g.pts[p];
+  const CellBox b = wave_uniform(cell_box(g, q, r2));
+  unsigned long long walked = 0;
+  const int ys = b.yb - b.ya + 1, rows = (b.zb - b.za + 1) * ys;
+  for (int r = row_first; r < rows; r += row_step) {
+    uint32_t ja, jb;
+    box_row(g, b, b.za + r / ys, b.ya + r % ys, ja, jb);
+    for (uint32_t j0 = ja; j0 < jb; j0 += 64) {
+      const uint32_t j = j0 + static_cast<uint32_t>(lane);
+      const bool won = j < jb && nc_try(g, nrm, owner, j, q, r2, sn, c_min, seed);
+      const unsigned long long wins = __ballot(won);
+      if (!wins) continue;
+      unsigned int base = 0;
+      if (lane == 0) base = atomicAdd(count, static_cast<unsigned int>(__popcll(wins)));
+      base = static_cast<unsigned int>(wave_uniform(static_cast<int>(base)));
+      if (won) put(base + static_cast<unsigned int>(__popcll(wins & ((1ull << lane) - 1ull))), j);
+    }
+    walked += jb - ja;
+  }
+  return walked;
+}
+
+// start of a call: every record free, order[rank in original order] = sorted position
+__global__ void nc_init_kernel(const uint32_t* __restrict__ perm, size_t n, uint32_t* __restrict__ owner,
+                               uint32_t* __restrict__ order) {
+  const size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  owner[i] = kNcFree;
+  order[perm[i]] = static_cast<uint32_t>(i);
+}
+
+// wide path: one level of one round, a wave per frontier record.  counts[parity] counts the next frontier
+// and is zero at the launch; the launch zeroes counts[parity ^ 1], which the host read after the level
+// before, for the level after.  next holds n entries (a call claims every record at most once).
+__global__ __launch_bounds__(256) void nc_expand_kernel(GridView g, const float4* __restrict__ nrm,
+                                                        uint32_t* __restrict__ owner,
+                                                        const uint32_t* __restrict__ frontier, uint32_t count, float r2,
+                                                        float4 sn, float c_min, uint32_t seed, uint32_t* __restrict__ next,
+                                                        unsigned int* __restrict__ counts, int parity,
+                                                        unsigned long long* __restrict__ ctr) {
+  const int lane = threadIdx.x & 63;
+  if (blockIdx.x == 0 && threadIdx.x == 0) counts[parity ^ 1] = 0;
+  unsigned int* next_count = counts + parity;
+  const uint32_t w = blockIdx.x * 4u + (threadIdx.x >> 6);  // 4 waves a block: no 32-bit wrap below 2^32 waves
+  if (w >= count) return;  // whole wave
+  const uint32_t p = static_cast<uint32_t>(wave_uniform(static_cast<int>(frontier[w])));
+  const unsigned long long walked =
+      nc_expand_one(g, nrm, owner, p, r2, sn, c_min, seed, next_count, lane, 0, 1, [&](unsigned int slot, uint32_t j) { next[slot] = j; });
+  slot_add<1>(ctr, w, kNcCtrSlots, lane, {walked});
+}
+
+// small path: ONE workgroup runs consecutive rounds with the frontier in LDS.  It finds the next seed
+// itself (a monotone cursor over `order`), expands level after level between barriers, and returns when
+// the cursor passes n (status 0) or when a round holds more than `limit` records after a level (status 1:
+// the wide path continues that round from `spill`, which received every next frontier in full; claims are
+// monotone, so the round's closure is the same whoever finishes it).  Loops: the cursor only advances
+// (at most n / kNcThreads + rounds turns), a level claims at least one record or ends its round (at most n
+// levels in a call), a box walk is bounded by the grid.
+constexpr int kNcThreads = 1024;
+// NcState (mgicp_internal.hpp): cursor in / out; status 0: the cursor passed n, 1: a round handed over -- then
+// seed (original index), seed_pos (its sorted position) and count (its frontier, spill[0 .. count));
+// rounds += rounds begun, walked += candidates walked by this launch.
+__global__ __launch_bounds__(kNcThreads) void nc_small_kernel(GridView g, uint32_t n, const float4* __restrict__ nrm,
+                                                              const uint32_t* __restrict__ order,
+                                                              uint32_t* __restrict__ owner, float r2, float c_min,
+                                                              uint32_t limit, uint32_t* __restrict__ spill,
+                                                              NcState* __restrict__ st) {
+  __shared__ uint32_t fr[2][kNcSmallCap];
+  __shared__ unsigned int s_cnt[2];
+  __shared__ uint32_t s_next;
+  __shared__ unsigned long long s_walked;
+  const int lane = threadIdx.x & 63;
+  const uint32_t wave = threadIdx.x >> 6;
+  constexpr uint32_t nw = kNcThreads / 64;
+  uint32_t cursor = st->cursor, rounds = 0, status = 0, h_seed = 0, h_pos = 0, h_count = 0;
+  unsigned long long walked = 0;
+  if (threadIdx.x == 0) s_walked = 0;
+  for (;;) {
+    uint32_t found = n;
+    while (cursor < n) {
+      __syncthreads();
+      if (threadIdx.x == 0) s_next = n;
+      __syncthreads();
+      const uint32_t r = cursor + threadIdx.x;
+      if (r < n && nc_owner(owner, order[r]) == kNcFree) atomicMin(&s_next, r);
+      __syncthreads();
+      found = s_next;
+      if (found < n) break;
+      cursor = cursor + kNcThreads < n ? cursor + kNcThreads : n;
+    }
+    if (found >= n) {
+      cursor = n;
+      break;
+    }
+    cursor = found + 1;
+    const uint32_t sp = order[found];
+    const uint32_t seed = __float_as_uint(g.pts[sp].w);
+    const float4 sn = nrm[sp];
+    if (threadIdx.x == 0) {
+      __hip_atomic_store(owner + sp, seed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      fr[0][0] = sp;
+      s_cnt[0] = 0;
+      s_cnt[1] = 0;
+    }
+    ++rounds;
+    uint32_t cnt = 1, members = 1;
+    int cur = 0;
+    __syncthreads();
+    while (cnt) {
+      uint32_t* nxt = fr[cur ^ 1];
+      for (uint32_t f = 0; f < cnt; ++f)  // every wave at every record, the box's rows dealt out among them
+        walked += nc_expand_one(g, nrm, owner, static_cast<uint32_t>(wave_uniform(static_cast<int>(fr[cur][f]))), r2, sn,
+                                c_min, seed, &s_cnt[cur ^ 1], lane, static_cast<int>(wave), static_cast<int>(nw),
+                                [&](unsigned int slot, uint32_t j) {
+                                  spill[slot] = j;
+                                  if (slot < kNcSmallCap) nxt[slot] = j;
+                                });
+      __syncthreads();
+      cnt = s_cnt[cur ^ 1];
+      if (threadIdx.x == 0) s_cnt[cur] = 0;  // the counter of the level after the next
+      cur ^= 1;
+      members += cnt;
+      __syncthreads();
+      if (cnt && members > limit) {
+        status = 1;
+        h_seed = seed;
+        h_pos = sp;
+        h_count = cnt;
+        break;
+      }
+    }
+    if (status) break;
+  }
+  if (lane == 0 && walked) atomicAdd(&s_walked, walked);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    st->cursor = cursor;
+    st->status = status;
+    st->seed = h_seed;
+    st->seed_pos = h_pos;
+    st->count = h_count;
+    st->rounds += rounds;
+    st->walked += s_walked;
+  }
+}
+
+// owner[] is now every record's round, and a round's seed is its smallest member: (seed, original index) at
+// the record's rank in original order, as cc_emit_kernel leaves them for the stable sort
+__global__ void nc_emit_kernel(const float4* __restrict__ pts, const uint32_t* __restrict__ perm, size_t n,
+                               const uint32_t* __restrict__ owner, uint32_t* __restrict__ keys,
+                               uint32_t* __restrict__ vals) {
+  const size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t c = perm[i];
+  keys[c] = owner[i];
+  vals[c] = __float_as_uint(pts[i].w);
+}
+
+hipError_t launch_nc_begin(const GridView& g, const uint32_t* perm, size_t n, const float* normals, float4* nrm,
+                           uint32_t* owner, uint32_t* order, hipStream_t s) {
+  if (!n) return hipSuccess;
+  nc_init_kernel<<<nblk(n), 256, 0, s>>>(perm, n, owner, order);
+  harris_pack_kernel<<<nblk(n), 256, 0, s>>>(g.pts, n, normals, nrm);
+  return hipGetLastError();
+}
+
+hipError_t launch_nc_small(const GridView& g, size_t n, const float4* nrm, const uint32_t* order, uint32_t* owner,
+                           float r2, float c_min, uint32_t limit, uint32_t* spill, NcState* state, hipStream_t s) {
+  nc_small_kernel<<<1, kNcThreads, 0, s>>>(g, static_cast<uint32_t>(n), nrm, order, owner, r2, c_min,
+                                           std::max(1u, std::min(limit, kNcSmallCap)), spill, state);
+  return hipGetLastError();
+}
+
+hipError_t launch_nc_expand(const GridView& g, const float4* nrm, uint32_t* owner, const uint32_t* frontier,
+                            uint32_t count, float r2, const float seed_normal[3], float c_min, uint32_t seed,
+                            uint32_t* next, unsigned int* counts, int parity, unsigned long long* ctr,
+                            hipStream_t s) {
+  if (!count) return hipSuccess;
+  const float4 sn = make_float4(seed_normal[0], seed_normal[1], seed_normal[2], 0.f);
+  nc_expand_kernel<<<nblk(static_cast<size_t>(count) * 64), 256, 0, s>>>(g, nrm, owner, frontier, count, r2, sn, c_min,
+                                                                         seed, next, counts, parity, ctr);
+  return hipGetLastError();
+}
+
+hipError_t launch_nc_emit(const GridView& g, const uint32_t* perm, size_t n, const uint32_t* owner, uint32_t* keys,
+                          uint32_t* vals, hipStream_t s) {
+  if (!n) return hipSuccess;
+  nc_emit_kernel<<<nblk(n), 256, 0, s>>>(g.pts, perm, n, owner, keys, vals);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
+// Dominant normals (InitialAlignment::obtainDominantNormals): per cluster the fp64 sum of its entries -- the
+// first member, then every member -- in the fixed tree of pair_moments_kernel, taken per cluster: entry k
+// of a cluster belongs to thread k % 256 of the cluster's block k / 256 (dn_partial_kernel), the cluster's
+// blocks then go through reduce_finish_kernel's loop and tree (dn_finish_kernel, one block per cluster).
+// ------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void dn_partial_kernel(const float* __restrict__ normals, const int* __restrict__ indices,
+                                                         const unsigned long long* __restrict__ offsets,
+                                                         const uint32_t* __restrict__ blk_cluster,
+                                                         const uint32_t* __restrict__ blk_first,
+                                                         double* __restrict__ partial) {
+  double acc[kRedVals];
+#pragma unroll
+  for (int v = 0; v < kRedVals; ++v) acc[v] = 0.0;
+  const uint32_t c = blk_cluster[blockIdx.x];
+  const unsigned long long k = static_cast<unsigned long long>(blockIdx.x - blk_first[c]) * 256u + threadIdx.x;
+  const unsigned long long size = offsets[c + 1] - offsets[c];
+  if (k <= size) {
+    const size_t m = static_cast<size_t>(indices[offsets[c] + (k ? k - 1 : 0)]);
+#pragma unroll
+    for (int r = 0; r < 3; ++r) acc[r] = static_cast<double>(normals[3 * m + r]);
+  }
+  block_reduce_store(acc, partial + static_cast<size_t>(blockIdx.x) * kRedVals);
+}
+
+// Eigen's normalize(): divided by the norm when the squared norm is > 0, else left as it is (a zero sum
+// stays zero, a NaN sum NaN); in fp64, rounded to float once
+__global__ __launch_bounds__(256) void dn_finish_kernel(const double* __restrict__ partial,
+                                                        const uint32_t* __restrict__ blk_first, float* __restrict__ out) {
+  __shared__ double tot[kRedVals];
+  double acc[kRedVals];
+#pragma unroll
+  for (int v = 0; v < kRedVals; ++v) acc[v] = 0.0;
+  const uint32_t c = blockIdx.x, b0 = blk_first[c], nb = blk_first[c + 1] - b0;
+  for (uint32_t b = threadIdx.x; b < nb; b += blockDim.x) {
+#pragma unroll
+    for (int v = 0; v < kRedVals; ++v) acc[v] += partial[static_cast<size_t>(b0 + b) * kRedVals + v];
+  }
+  block_reduce_store(acc, tot);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double x = tot[0], y = tot[1], z = tot[2];
+    const double z2 = (x * x + y * y) + z * z;
+    if (z2 > 0.0) {
+      const double nrm = sqrt(z2);
+      x /= nrm;
+      y /= nrm;
+      z /= nrm;
+    }
+    out[3 * static_cast<size_t>(c)] = static_cast<float>(x);
+    out[3 * static_cast<size_t>(c) + 1] = static_cast<float>(y);
+    out[3 * static_cast<size_t>(c) + 2] = static_cast<float>(z);
+  }
+}
+
+hipError_t launch_dominant_normals(const float* normals, const int* indices, const unsigned long long* offsets,
+                                   const uint32_t* blk_cluster, const uint32_t* blk_first, size_t n_blocks,
+                                   size_t n_clusters, double* partial, float* out, hipStream_t s) {
+  if (!n_clusters) return hipSuccess;
+  dn_partial_kernel<<<static_cast<unsigned>(n_blocks), 256, 0, s>>>(normals, indices, offsets, blk_cluster, blk_first, partial);
+  dn_finish_kernel<<<static_cast<unsigned>(n_clusters), 256, 0, s>>>(partial, blk_first, out);
+  return hipGetLastError();
+}
+
 size_t sort_scratch_bytes(size_t n, int bits) {
   size_t bytes = 0;
   (void)hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, static_cast<const uint32_t*>(nullptr),
@@ -6083,6 +6380,12 @@ hipError_t preload_kernels(void* pinned, size_t pinned_bytes, hipStream_t s) {
       reinterpret_cast<const void*>(&o2o_min_kernel),
       reinterpret_cast<const void*>(&o2o_flag_kernel),
       reinterpret_cast<const void*>(&o2o_scatter_kernel),
+      reinterpret_cast<const void*>(&nc_init_kernel),
+      reinterpret_cast<const void*>(&nc_small_kernel),
+      reinterpret_cast<const void*>(&nc_expand_kernel),
+      reinterpret_cast<const void*>(&nc_emit_kernel),
+      reinterpret_cast<const void*>(&dn_partial_kernel),
+      reinterpret_cast<const void*>(&dn_finish_kernel),
   };
   for (const void* f : fns) {
     hipFuncAttributes attr;

@@ -67,6 +67,7 @@ class GICPEngine:
         self._converged = False
         self._final = np.eye(4, dtype=np.float32)
         self.last_result = None
+        self.last_dominant_ms = None  # dominant_normals: ms from its first launch to the result on the host
         for k, v in {**GICPEngine.DEFAULT_OPTIONS, **(options or {})}.items():
             self.debug_option(k, v)
 
@@ -511,6 +512,54 @@ class GICPEngine:
         info = {f: getattr(ci, f) for f, _ in ci._fields_}
         info["offsets"] = off[:ci.n_clusters + 1]
         return clusters, labels[:n], info
+
+    def normal_clusters(self, cloud, normals, tolerance: float, eps_angle: float, min_size: int = 1, max_size: int = 0):
+        """pcl::extractEuclideanClusters with normals (InitialAlignment::obtainNormalsCluster): (clusters,
+        labels, info).  PCL's serial rounds in ascending seed: a round takes what its seed reaches by links
+        through unprocessed records whose normal is within eps_angle of the SEED's.  `clusters`: int32 index
+        arrays in ascending seed, members ascending; `labels`: per record the rank of its cluster or -1;
+        `normals` is float32 [n, 3] or [n, 4], one per record of `cloud`."""
+        min_size, max_size = int(min_size), int(max_size)
+        if min_size < 0 or max_size < 0:  # would wrap to a huge size_t
+            raise ValueError(f"normal_clusters: min_size {min_size} / max_size {max_size} must be >= 0")
+        _keep, ptr, n, stride = self._cloud_arg(cloud)
+        nrm = np.ascontiguousarray(normals, dtype=np.float32)
+        if nrm.ndim != 2 or nrm.shape[1] < 3 or len(nrm) != n:
+            raise ValueError(f"normals must be [{n}, 3] or [{n}, 4], got {nrm.shape}")
+        labels = np.full(max(n, 1), -1, np.int32)
+        indices = np.zeros(max(n, 1), np.int32)
+        offsets = np.zeros(n + 1, np.uintp)
+        ci = _lib.MgicpNormalClusterInfo()
+        self._check(self._lib.mgicp_normal_clusters(
+            self._h, ctypes.c_void_p(ptr), n, stride, ctypes.c_void_p(nrm.ctypes.data), 4 * nrm.shape[1],
+            float(tolerance), float(eps_angle), min_size, max_size, labels.ctypes.data, indices.ctypes.data,
+            offsets.ctypes.data, ctypes.byref(ci)), "normal_clusters")
+        off = offsets.astype(np.int64)
+        nc = int(ci.n_clusters)
+        clusters = [indices[off[c]:off[c + 1]].copy() for c in range(nc)]
+        info = {f: getattr(ci, f) for f, _ in ci._fields_}
+        info["offsets"] = off[:nc + 1]
+        return clusters, labels[:n], info
+
+    def dominant_normals(self, normals, clusters):
+        """InitialAlignment::obtainDominantNormals: float32 [len(clusters), 3], per cluster the normalised sum of
+        its members' normals with the first member counted twice (as the reference does).  `clusters`: index
+        arrays into `normals` (float32 [n, 3] or [n, 4]).  The call's device time lands in last_dominant_ms."""
+        nrm = np.ascontiguousarray(normals, dtype=np.float32)
+        if nrm.ndim != 2 or nrm.shape[1] < 3:
+            raise ValueError(f"normals must be [n, 3] or [n, 4], got {nrm.shape}")
+        members = [np.ascontiguousarray(c, dtype=np.int32).reshape(-1) for c in clusters]
+        nc = len(members)
+        indices = np.concatenate(members).astype(np.int32) if nc else np.zeros(0, np.int32)
+        offsets = np.zeros(nc + 1, np.uintp)
+        offsets[1:] = np.cumsum([len(m) for m in members])
+        out = np.zeros((max(nc, 1), 3), np.float32)
+        ms = ctypes.c_double()
+        self._check(self._lib.mgicp_dominant_normals(
+            self._h, ctypes.c_void_p(nrm.ctypes.data), len(nrm), 4 * nrm.shape[1], ctypes.c_void_p(indices.ctypes.data),
+            offsets.ctypes.data, nc, out.ctypes.data, ctypes.byref(ms)), "dominant_normals")
+        self.last_dominant_ms = ms.value
+        return out[:nc]
 
     def voxel_grid(self, cloud: PointCloudRGB, leaf, min_points_per_voxel: int = 0) -> PointCloudRGB:
         """pcl::VoxelGrid<PointXYZRGB>::filter (Filter::downsampleCloud) -> a new cloud."""

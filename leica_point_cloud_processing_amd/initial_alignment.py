@@ -7,6 +7,11 @@ nearest target descriptor of every source descriptor, and the three steps that t
 into rigid_tf_: rejectCorrespondences (RANSAC), rejectOneToOneCorrespondences and estimateTransform (SVD).
 runKeypointsBasedAlgorithm chains them as the reference does, so BOUNDARY and HARRIS run on the engine from
 the normals to the transform.  The normals they take come from gicp_alignment.getNormals (Utils::getNormals).
+
+Of the NORMALS method: obtainNormalsCluster (normal-conditioned Euclidean clustering) and obtainDominantNormals,
+chained by runNormalsBasedAlgorithm after the boundary keypoints as the reference does.  Out of scope:
+getTransformationFromNormals and its helpers (normalsCorrespondences, findIdx, matrixFromAngles) -- O(clusters^2)
+host arithmetic of the reference's own on at most 40 normals, which stays in the catkin package.
 """
 from __future__ import annotations
 
@@ -21,6 +26,9 @@ RADIUS_FACTOR = 1.4                # radius_factor_ (the constructor's default)
 HARRIS_THRESHOLD = np.float32(1e-6)  # detector.setThreshold(1e-6): PCL's threshold_ is a float
 RANSAC_INLIER_THRESHOLD = 1.5      # rejector.setInlierThreshold(1.5)
 RANSAC_MAX_ITERATIONS = 1000       # CorrespondenceRejectorSampleConsensus's default max_iterations_
+NORMALS_CLUSTER_TOLERANCE = float(np.float32(0.05))  # const float tolerance = 0.05f
+NORMALS_CLUSTER_EPS_ANGLE = 20 * (np.pi / 180.0)     # const double eps_angle = 20 * (M_PI / 180.0)
+NORMALS_CLUSTER_PERCENTAJE = 0.025                   # min_cluster_size = (int)normals->size() * PERCENTAJE
 
 
 def obtainBoundaryKeypoints(cloud, normals, engine: GICPEngine | None = None):
@@ -187,3 +195,58 @@ def runKeypointsBasedAlgorithm(source, target, method: str = "BOUNDARY", radius_
     steps["correspondences_final"] = corr
     T, exists = estimateTransform(sk, tk, corr, engine)
     return T, exists, steps
+
+
+def obtainNormalsCluster(cloud, normals, engine: GICPEngine | None = None):
+    """InitialAlignment::obtainNormalsCluster (src/InitialAlignment.cpp:130-161): pcl::extractEuclideanClusters
+    with normals at a tolerance of 0.05f, 20 degrees, a minimum size of (int)n * 0.025 truncated to unsigned
+    and no cap.  Returns the clusters, int32 index arrays in ascending seed; when none is found, the
+    reference's fallback of one cluster 0 .. n - 1."""
+    if engine is None:
+        from .filter import _engine
+
+        engine = _engine()
+    normals = np.asarray(normals, dtype=np.float32)
+    n = len(normals)
+    min_size = int(int(n) * NORMALS_CLUSTER_PERCENTAJE)
+    clusters, _labels, _info = engine.normal_clusters(cloud, normals, NORMALS_CLUSTER_TOLERANCE,
+                                                      NORMALS_CLUSTER_EPS_ANGLE, min_size, 0)
+    if len(clusters) == 0:
+        size = cloud.size() if isinstance(cloud, PointCloudRGB) else len(np.asarray(cloud).reshape(-1, 3))
+        clusters = [np.arange(size, dtype=np.int32)]
+    return clusters
+
+
+def obtainDominantNormals(normals, clusters, engine: GICPEngine | None = None):
+    """InitialAlignment::obtainDominantNormals (src/InitialAlignment.cpp:163-187): float32 [len(clusters), 3],
+    per cluster the normalised sum of its normals, the first member counted twice as the reference does."""
+    if engine is None:
+        from .filter import _engine
+
+        engine = _engine()
+    return engine.dominant_normals(normals, clusters)
+
+
+def runNormalsBasedAlgorithm(source, target, engine: GICPEngine | None = None):
+    """InitialAlignment::runNormalsBasedAlgorithm (src/InitialAlignment.cpp:81-115) up to the dominant normals:
+    boundary keypoints of both clouds, the extraction of the non-boundary records (cloud and normals),
+    obtainNormalsCluster and obtainDominantNormals.  `source` and `target` are (cloud, normals) pairs.  Returns
+    (source_dominant_normals, target_dominant_normals, steps); getTransformationFromNormals is out of scope
+    (module docstring)."""
+    if engine is None:
+        from .filter import _engine
+
+        engine = _engine()
+    steps, dominant = {}, []
+    for name, (cloud, normals) in (("source", source), ("target", target)):
+        normals = np.asarray(normals, dtype=np.float32)
+        _status, _kp, non_boundary = obtainBoundaryKeypoints(cloud, normals, engine)
+        xyz = np.ascontiguousarray(_xyz(cloud)[non_boundary], np.float32)
+        nrm = np.ascontiguousarray(normals[non_boundary], np.float32)
+        clusters = obtainNormalsCluster(xyz, nrm, engine)
+        dominant.append(obtainDominantNormals(nrm, clusters, engine))
+        steps[name + "_non_boundary_indices"] = non_boundary
+        steps[name + "_cloud_no_boundary"] = xyz
+        steps[name + "_normals_no_boundary"] = nrm
+        steps[name + "_cluster_indices"] = clusters
+    return dominant[0], dominant[1], steps
